@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — estimator-steps/s of the EKF + 20-step-MHE hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Both forms work for N > 1: called plainly (no WORLD_SIZE in the environment), `main()` starts the N ranks itself as a
@@ -276,6 +276,26 @@ def pipelined_leg_multi(env, dist, p, B, sd, total, K, world, rank):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, out, info):
+    """--dump-outputs: what the timed path handed its caller after the last timed step — the estimator outputs (dekf_get) and the
+    solver report (dekf_get_solver_info) of every instance of this rank's shard — as <out_dir>/<name>.npy in float64, so that two
+    builds run with the same arguments (same seeded logs) can be compared array for array.  Over DUMP_LIMIT_BYTES in all, the same
+    fixed, seeded sample of instances is kept in every array (instance_index.npy says which)."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in list(out.items()) + list(info.items())}
+    B = len(arrays["x"])
+    per_instance = sum(a[0].nbytes for a in arrays.values()) + 8
+    idx = np.arange(B)
+    if per_instance * B > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(B, DUMP_LIMIT_BYTES // per_instance, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a[idx])
+    np.save(os.path.join(out_dir, "instance_index.npy"), idx.astype(np.float64))
+
+
 def default_batch(gpus):
     """instances per GPU when --batch is not given: configs[1] at one GPU; at N > 1 the per-rank share of configs[3]
     (65 536 over 8 GPUs), so that the driver's plain `bench.py --gpus 8` IS that configuration"""
@@ -430,6 +450,8 @@ def run_bench(args, env, rank, world):
 
     out = est.get()
     info = est.solver_info()
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        dump_outputs(args.dump_outputs, out, info)
     solved = float((out["status"] == 1).mean())
     v_err = float(np.abs(out["x"][:, 3:6] - s["gt_v_s"][total - 1]).max())
 
@@ -550,6 +572,8 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--batch", type=int, default=None, help="instances per GPU (default 4096 at --gpus 1, else 8192)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed "
+                    "(estimator outputs and solver report of rank 0's instances) to DIR/<name>.npy in float64")
     ap.add_argument("--no-allgather", action="store_true")
     ap.add_argument("--pipelined-leg", action="store_true", help="after the line's own K steps, run them once more with solve_pipeline = 1 "
                     "and report that as with_step_pipelining beside value (at N > 1: on every rank, with the pipelined handle's all-gather).  Off by default: the extra launches of the same "

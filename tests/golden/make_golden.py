@@ -5,6 +5,9 @@
 go1_kin.npz   TRUE reference vectors: inputs/outputs of the reference's own FROST-generated Go1
               kinematics (src/go1_example/src/Expressions/*.cc compiled as oracle/_ref/libgo1kin.so),
               driven exactly as go1Sub::lo_callback drives them (go1Sub.cpp:64-125).
+go1_kin_random.npz
+              the same library at 2000 seeded random joint vectors over the whole joint range (positions and
+              Jacobians of all four feet), so that the front-end is held to the reference code without it.
 ekf_trace.npz / mhe_trace.npz
               regression pins produced by the CPU oracle (the reference ships no vectors for these
               paths and cannot be built here — SURVEY.md §8c); inputs + expected outputs.
@@ -49,6 +52,35 @@ def go1_kin():
             J[i, l] = Jfull[:, 6 + 4 * l:6 + 4 * l + 3]
     np.savez_compressed(os.path.join(HERE, "go1_kin.npz"), joint_position=q, p_ib=p_ib, p_imu_2_foot=p, J_imu_2_foot=J)
     print("go1_kin.npz", p.shape, J.shape)
+
+
+def go1_kin_random():
+    lib = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libgo1kin.so"))
+    dp = C.POINTER(C.c_double)
+
+    def call(sym, var, n):
+        f = getattr(lib, sym)
+        f.argtypes, f.restype = [dp, dp], None
+        out = np.zeros(n)
+        f(out.ctypes.data_as(dp), var.ctypes.data_as(dp))
+        return out
+
+    rng = np.random.default_rng(99)
+    n = 2000
+    q = rng.uniform(-1.2, 1.2, (n, 12))
+    q[:, 1::3] = rng.uniform(-1.5, 3.5, (n, 4))       # thigh range
+    q[:, 2::3] = rng.uniform(-2.7, -0.5, (n, 4))      # calf range
+    p_ib = np.array([0.01592, 0.06659, 0.00617])
+    p, J = np.zeros((n, 4, 3)), np.zeros((n, 4, 3, 3))
+    for i in range(n):
+        var = np.zeros(22)
+        for l in range(4):
+            var[6 + 4 * l:6 + 4 * l + 3] = q[i, 3 * l:3 * l + 3]
+        for l, name in enumerate(["FR", "FL", "RR", "RL"]):
+            p[i, l] = call(f"_ZN11SymFunction{len(name) + 9}{name}_foot_rawEPdPKd", var, 3) + p_ib
+            J[i, l] = call(f"_ZN11SymFunction{len(name) + 6}J_{name}_rawEPdPKd", var, 66).reshape(22, 3).T[:, 6 + 4 * l:6 + 4 * l + 3]
+    np.savez_compressed(os.path.join(HERE, "go1_kin_random.npz"), joint_position=q, p_ib=p_ib, p_imu_2_foot=p, J_imu_2_foot=J)
+    print("go1_kin_random.npz", p.shape, J.shape)
 
 
 def ekf_trace():
@@ -98,5 +130,6 @@ def mhe_trace():
 
 if __name__ == "__main__":
     go1_kin()
+    go1_kin_random()
     ekf_trace()
     mhe_trace()

@@ -164,3 +164,32 @@ def test_workload_names_and_default_shards():
     w8 = bench.workload_name(8192, 8, 20)
     assert "batch=65536" in w8 and "configs[3]" in w8 and "8xMI355X" in w8
     assert "configs[3]" not in bench.workload_name(4096, 8, 20).replace("per-rank share of BASELINE.json configs[3]", "")
+
+
+def test_dump_outputs_writes_what_the_last_timed_step_returned(tmp_path):
+    """--dump-outputs DIR: the arrays the timed path hands its caller after its last step, one .npy each, in float64"""
+    out = tmp_path / "dump"
+    r = _bench_cli(["--steps", "3", "--warmup", "2", "--batch", "5", "--bench-env", "bench_stand_in:make_env", "--dump-outputs", str(out)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    got = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert set(got) == {"x", "v_b", "status", "iters", "rho_updates", "instance_index"}
+    assert all(a.dtype == np.float64 and len(a) == 5 for a in got.values())
+    last = 64 + 3 - 1   # window fill + warm-up end at tick 64, then exactly 3 timed steps
+    assert np.array_equal(got["v_b"], np.arange(5)[:, None] * 1000.0 + last + np.arange(3)[None, :] * 0.25)
+    assert np.array_equal(got["instance_index"], np.arange(5)) and (got["status"] == 1).all()
+
+
+def test_dump_outputs_samples_the_same_instances_when_over_the_limit(tmp_path, monkeypatch):
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 100 * 8 * 7)   # 7 doubles per instance: x (4), status, iters, index
+    B = 1000
+    out = {"x": np.arange(B * 4, dtype=np.float64).reshape(B, 4), "status": np.ones(B, np.int32)}
+    bench.dump_outputs(str(tmp_path / "a"), out, {"iters": np.arange(B, dtype=np.int32)})
+    bench.dump_outputs(str(tmp_path / "b"), out, {"iters": np.arange(B, dtype=np.int32)})
+    idx = np.load(tmp_path / "a" / "instance_index.npy").astype(np.int64)
+    assert len(idx) == 100 and len(np.unique(idx)) == 100
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "instance_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "x.npy"), out["x"][idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "iters.npy"), idx.astype(np.float64))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) < 100 * 8 * 7 + 5 * 256

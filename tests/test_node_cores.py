@@ -1,7 +1,7 @@
 """ROS2-free cores of the reference's two nodes: parameter files, callbacks, timer logic.
 
 CPU: the parameter readers (Python and C++) agree with each other, with the defaults the reference's nodes
-declare and — when the reference is mounted — with its own parameters_go1.yaml; the replay program compiles
+declare and with its own parameters_go1.yaml (tests/golden/); the replay program compiles
 and links.  GPU: a synthetic message sequence replayed through orien_sub -> est_sub (raw joint states,
 kinematics on the device) reproduces the oracle's estimates and writes the reference's log format.
 """
@@ -19,7 +19,8 @@ from decentralized_ekf_mhe_amd.streams import make_streams
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "decentralized_ekf_mhe_amd", "csrc")
-REF_YAML = "/root/reference/src/go1_example/config/parameters_go1.yaml"
+# the reference's src/go1_example/config/parameters_go1.yaml, stored as a fixture
+REF_YAML = os.path.join(ROOT, "tests", "golden", "parameters_go1.yaml")
 
 
 def _build(tmp_path, name):
@@ -226,7 +227,6 @@ def test_cpp_reader_agrees_with_pyyaml_on_generated_files(tmp_path):
     check()
 
 
-@pytest.mark.skipif(not os.path.exists(REF_YAML), reason="reference not mounted")
 def test_reference_go1_file_gives_go1_params(tmp_path):
     p, node = load_ros_params(REF_YAML)
     assert _fields(p) == _fields(go1_params())
