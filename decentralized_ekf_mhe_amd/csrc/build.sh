@@ -51,7 +51,7 @@ else
                 if grep -q "Illegal instruction detected\|LLVM ERROR\|PLEASE submit a bug report" "$T/ru_$m.txt"; then
                     cp "$T/ru_$m.txt" "$T/first_$m.txt"
                     echo "build.sh: kernel set $m: compiler crash with -mllvm -disable-machine-licm, retrying without it" >&2
-                    { echo "set $m: first attempt (with -disable-machine-licm) died:"; grep -v "remark:\|^ *[0-9]* | \|^ *| " "$T/first_$m.txt" | head -20; } >> "$T/ru_notes.txt"
+                    { echo "set $m: first attempt (with -disable-machine-licm) died:"; grep -v "remark:\|^ *[0-9]* | \|^ *| \|^In file included from " "$T/first_$m.txt" | head -20; } >> "$T/ru_notes.txt"
                     $HIPCC $FLAGS -Rpass-analysis=kernel-resource-usage -c -DDEKF_KSET=$m -DDEKF_KSET_ONLY -o "$T/k_$m.o" kernels.hip $EXTRA 2> "$T/ru_$m.txt" \
                         && echo "set $m: compiled WITHOUT -disable-machine-licm (retry)" >> "$T/ru_notes.txt" && return 0
                 fi;;
@@ -71,8 +71,8 @@ else
     for p in "${pids[@]}"; do wait "$p" || rc=1; done
     [ $rc -eq 0 ] || { echo "build failed"; exit 1; }
     $HIPCC --offload-arch=gfx950 -fPIC -shared -o "$OUT" "$T"/*.o -ldl
-    # (warnings of the units, if any, to the terminal; the remarks to the file)
-    cat "$T"/ru_*.txt | grep -v "remark:\|^ *[0-9]* | \|^ *| " >&2 || true
+    # (warnings of the units, if any, to the terminal, without the include chain in front of the solve kernels' remarks; the remarks to the file)
+    cat "$T"/ru_*.txt | grep -v "remark:\|^ *[0-9]* | \|^ *| \|^In file included from " >&2 || true
     { echo "# compiler resource remarks of $(basename "$OUT"), $(date -u +%Y-%m-%dT%H:%MZ), flags: $FLAGS $EXTRA; no-machine-LICM sets: $NO_MLICM";
       cat "$T"/ru_notes.txt 2>/dev/null || true; cat "$T"/ru_*.txt | grep "remark:" | sed 's/^.*remark: *//; s/ *\[-Rpass-analysis=kernel-resource-usage\]//'; } > "${OUT%.so}_resource_usage.txt"
 fi

@@ -22,31 +22,11 @@ __global__ void k_ekf_tick(DevCfg c, DevState s, int count);
 __global__ void k_mhe_initialize(DevCfg c, DevState s);
 __global__ void k_mhe_assemble(DevCfg c, DevState s, int T, int pushes);
 __global__ void k_mhe_marginalize_early(DevCfg c, DevState s, int T);
-// every solve kernel and its twin with OSQP's polishing step (kernels.hip: DEKF_SOLVE_KERNEL_BODY)
-#define DEKF_DECL_K(NAME)                                                              \
+// every solve kernel and its twin with OSQP's polishing step (solve_kernels.def)
+#define DEKF_SOLVE_KERNEL(NAME, ...)                                                   \
     __global__ void NAME(DevCfg c, DevState s, int kstart, int K, int gws_len);        \
     __global__ void NAME##_pol(DevCfg c, DevState s, int kstart, int K, int gws_len);
-#define DEKF_DECL_SOLVE(LEGS) DEKF_DECL_K(k_mhe_solve_ll_##LEGS) DEKF_DECL_K(k_mhe_solve_lg_##LEGS) DEKF_DECL_K(k_mhe_solve_gg_##LEGS)
-DEKF_DECL_K(k_mhe_solve_ll_4_n20)
-DEKF_DECL_K(k_mhe_solve_lg_2_n20)
-#ifndef DEKF_NO_R3
-DEKF_DECL_K(k_mhe_solve_r3_4_n20)
-DEKF_DECL_K(k_mhe_solve_r3_2_n20)
-DEKF_DECL_K(k_mhe_solve_r4_4_n20)
-DEKF_DECL_K(k_mhe_solve_r4_2_n20)
-#endif
-DEKF_DECL_SOLVE(1)
-#ifndef DEKF_NO_RR
-DEKF_DECL_K(k_mhe_solve_rr_1)
-#endif
-DEKF_DECL_SOLVE(2)
-DEKF_DECL_SOLVE(3)
-DEKF_DECL_SOLVE(4)
-#define DEKF_DECL_SOLVE_FOOT(LEGS) DEKF_DECL_K(k_mhe_solve_foot_lg_##LEGS) DEKF_DECL_K(k_mhe_solve_foot_gg_##LEGS)
-DEKF_DECL_SOLVE_FOOT(1)
-DEKF_DECL_SOLVE_FOOT(2)
-DEKF_DECL_SOLVE_FOOT(3)
-DEKF_DECL_SOLVE_FOOT(4)
+#include "solve_kernels.def"
 __global__ void k_gap();
 __global__ void k_kf_initialize(DevCfg c, DevState s);
 __global__ void k_kf_update(DevCfg c, DevState s, int pushes);
@@ -139,6 +119,83 @@ namespace {
 dekf_status fail(dekf_status st, const char* msg) {
     g_err = msg;
     return st;
+}
+
+// The solve kernels as dekf_create selects them: every row of solve_kernels.def with its polishing twin
+typedef void (*SolveFn)(DevCfg, DevState, int, int, int);
+enum class SolveRole { ll, lg, gg, foot_lg, foot_gg, r3, r4, rr };
+struct SolveKernel {
+    SolveRole role;
+    int legs, nfix;  // solve_window_t's L and NFIX (0: run-time horizon)
+    SolveFn fn, fn_pol;
+    const char *name, *name_pol;
+};
+#define DEKF_LEGS_(L, ...) L
+#define DEKF_NFIX_(L, FACTOR_LDS, PA_LDS, NFIX, ...) NFIX
+#define DEKF_SOLVE_KERNEL(NAME, ROLE, THREADS, WAVES, LOOP, ...) \
+    {SolveRole::ROLE, DEKF_LEGS_(__VA_ARGS__), DEKF_NFIX_(__VA_ARGS__, 0, 0), NAME, NAME##_pol, #NAME, #NAME "_pol"},
+const SolveKernel solve_kernels[] = {
+#include "solve_kernels.def"
+};
+
+// the kernel of ROLE for L legs: the one compiled for the horizon N if there is one, else the one with a run-time horizon
+const SolveKernel* solve_kernel(SolveRole role, int L, int N) {
+    const SolveKernel* any = nullptr;
+    for (const SolveKernel& k : solve_kernels) {
+        if (k.role != role || k.legs != L) continue;
+        if (k.nfix == N) return &k;
+        if (k.nfix == 0) any = &k;
+    }
+    return any;
+}
+
+// A family of full-window kernels (K == N): the shapes it covers are the rows of its role in solve_kernels.def
+struct FullWindowFamily {
+    SolveRole role;
+    bool eligible;     // the caller's cap on workgroups per CU admits the family
+    int threads;       // workgroup size
+    size_t lds;        // dynamic LDS of one workgroup (SolveLayout::*_lds_bytes)
+    bool (SolveLayout::*fits)(int, size_t) const;
+    int max_per_cu;    // workgroups per CU the kernel is compiled for
+    bool query;        // true: workgroups per CU from the occupancy query (clamped to max_per_cu and the cap), taken when that is more
+                       // than the window-fill kernel's; false: max_per_cu, taken when the grid grows
+    const char* ab_grid_env;    // DEKF_AB_KNOBS: another persistent grid
+    const char* ab_round5_env;  // DEKF_AB_KNOBS: the round-5 rule, taken only when the grid grows too
+};
+
+// makes f the handle's full-window kernel if f's rule takes it (h->solve_grid: the window-fill kernel's grid, per_cu its residency)
+bool take_full_window(dekf_handle h, const FullWindowFamily& f, const SolveLayout& lay, int per_cu, int cap, int cus, int batch) {
+    const SolveKernel* k = f.eligible && !h->c.ft ? solve_kernel(f.role, h->c.L, h->c.N) : nullptr;
+    if (!k) return false;
+    const SolveFn fn = h->c.polish ? k->fn_pol : k->fn;
+    // the kernel's static LDS (reduction scratch of wave.h) counts against the same allocation as the dynamic part
+    hipFuncAttributes fa;
+    size_t static_lds = 512;
+    if (hipFuncGetAttributes(&fa, (const void*)fn) == hipSuccess) static_lds = fa.sharedSizeBytes;
+    if (!(lay.*f.fits)(h->c.L, static_lds)) return false;
+    if (f.lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds);
+    int pcf = f.max_per_cu;
+    if (f.query) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pcf, (const void*)fn, f.threads, f.lds) != hipSuccess || pcf < 1) pcf = 1;
+        if (pcf > f.max_per_cu) pcf = f.max_per_cu;  // the query over-reports: the *_fits rule has decided that max_per_cu fit
+        if (cap > 0 && pcf > cap) pcf = cap;
+    }
+    const long slots = (long)pcf * cus;
+    int grid = (int)(slots < batch ? slots : batch);
+#ifdef DEKF_AB_KNOBS  // A/B builds only (tools/r4_check.py)
+    if (const char* ge = f.ab_grid_env ? getenv(f.ab_grid_env) : nullptr) { const int gv = atoi(ge); if (gv > 0 && gv <= batch) grid = gv; }
+#endif
+    bool take = f.query ? pcf > per_cu : grid > h->solve_grid;
+#ifdef DEKF_AB_KNOBS
+    if (f.ab_round5_env && getenv(f.ab_round5_env)) take = take && grid > h->solve_grid;
+#endif
+    if (!take) return false;
+    h->solve_kernel_full = fn;
+    h->solve_name_full = h->c.polish ? k->name_pol : k->name;
+    h->solve_grid_full = grid;
+    h->solve_threads_full = f.threads;
+    h->lds_solve_full = f.lds;
+    return true;
 }
 
 dekf_status ensure_stage(dekf_handle h, size_t bytes) {
@@ -266,35 +323,22 @@ dekf_status dekf_create(const dekf_params* p, int batch, int device, void* strea
     // diagnostic build only: DEKF_DEBUG_LDS_PAD=<bytes> inflates the request (e.g. to force one workgroup per CU)
     if (const char* pad = getenv("DEKF_DEBUG_LDS_PAD")) h->lds_solve += (size_t)atol(pad);
 #endif
-    typedef void (*SolveFn)(DevCfg, DevState, int, int, int);
-#ifndef DEKF_R4_SELECT
-#define DEKF_R4_SELECT(cap) ((cap) == 4)
-#endif
     {
-        struct Named { SolveFn fn; const char* name; SolveFn fn_pol; const char* name_pol; };
-#define DEKF_K(sym) {sym, #sym, sym##_pol, #sym "_pol"}
-        static const Named table[4][3] = {
-            {DEKF_K(k_mhe_solve_ll_1), DEKF_K(k_mhe_solve_lg_1), DEKF_K(k_mhe_solve_gg_1)}, {DEKF_K(k_mhe_solve_ll_2), DEKF_K(k_mhe_solve_lg_2), DEKF_K(k_mhe_solve_gg_2)},
-            {DEKF_K(k_mhe_solve_ll_3), DEKF_K(k_mhe_solve_lg_3), DEKF_K(k_mhe_solve_gg_3)}, {DEKF_K(k_mhe_solve_ll_4), DEKF_K(k_mhe_solve_lg_4), DEKF_K(k_mhe_solve_gg_4)}};
-        Named pick = table[c.L - 1][lay.pa_in_lds() ? 0 : (lay.factor_in_lds() ? 1 : 2)];
-        if (c.L == 4 && c.N == 20 && lay.pa_in_lds()) pick = DEKF_K(k_mhe_solve_ll_4_n20);
-        if (c.L == 2 && c.N == 20 && lay.factor_in_lds() && !lay.pa_in_lds()) pick = DEKF_K(k_mhe_solve_lg_2_n20);
-        if (c.ft) {  // foot-position states: their own kernel family (two rows per block in the solve)
-            static const Named foot[4][2] = {{DEKF_K(k_mhe_solve_foot_lg_1), DEKF_K(k_mhe_solve_foot_gg_1)}, {DEKF_K(k_mhe_solve_foot_lg_2), DEKF_K(k_mhe_solve_foot_gg_2)},
-                                             {DEKF_K(k_mhe_solve_foot_lg_3), DEKF_K(k_mhe_solve_foot_gg_3)}, {DEKF_K(k_mhe_solve_foot_lg_4), DEKF_K(k_mhe_solve_foot_gg_4)}};
-            pick = foot[c.L - 1][lay.factor_in_lds() ? 0 : 1];
-        }
+        // the placement of the factor (SolveLayout), or the foot-position states' own family (two rows per block in the solve)
+        const SolveRole role = c.ft ? (lay.factor_in_lds() ? SolveRole::foot_lg : SolveRole::foot_gg)
+                                    : (lay.pa_in_lds() ? SolveRole::ll : (lay.factor_in_lds() ? SolveRole::lg : SolveRole::gg));
+        const SolveKernel* pick = solve_kernel(role, c.L, c.N);
         // osqp.polish: the twin that carries the polishing step
-        h->solve_kernel = c.polish ? pick.fn_pol : pick.fn;
-        h->solve_name = c.polish ? pick.name_pol : pick.name;
+        h->solve_kernel = c.polish ? pick->fn_pol : pick->fn;
+        h->solve_name = c.polish ? pick->name_pol : pick->name;
 #ifdef DEKF_PROFILE
         // diagnostic build only: DEKF_DEBUG_PLACEMENT=1|2 forces the _lg / _gg placement (2 also shrinks the LDS request)
         if (const char* pl = getenv("DEKF_DEBUG_PLACEMENT")) {
             int p = atoi(pl);
             if ((p == 1 || p == 2) && !c.ft) {
-                const Named& t = table[c.L - 1][p];
-                h->solve_kernel = c.polish ? t.fn_pol : t.fn;
-                h->solve_name = c.polish ? t.name_pol : t.name;
+                const SolveKernel* t = solve_kernel(p == 1 ? SolveRole::lg : SolveRole::gg, c.L, 0);
+                h->solve_kernel = c.polish ? t->fn_pol : t->fn;
+                h->solve_name = c.polish ? t->name_pol : t->name;
             }
             // the _gg kernels carve D, E, bounds and R behind the iterates when SolveLayout::gg_consts_in_lds() says so
             if (p == 2) h->lds_solve = (size_t)(lay.vec + (lay.gg_consts_in_lds() ? lay.gg_consts() : 0)) * sizeof(double);
@@ -317,95 +361,24 @@ dekf_status dekf_create(const dekf_params* p, int batch, int device, void* strea
     if (cap > 0 && per_cu > cap) per_cu = cap;
     long slots = (long)per_cu * prop.multiProcessorCount;
     h->solve_grid = (int)(slots < batch ? slots : batch);
-#ifndef DEKF_NO_R3
-    // Four workgroups of three wavefronts per CU (round 6, admm_chunk_r4): solve_workgroups_per_cu = DEKF_R4_SELECT selects them
-    if (!c.ft && c.N == 20 && (c.L == 4 || c.L == 2) && DEKF_R4_SELECT(cap)) {
-        const SolveFn full = c.polish ? (c.L == 4 ? k_mhe_solve_r4_4_n20_pol : k_mhe_solve_r4_2_n20_pol) : (c.L == 4 ? k_mhe_solve_r4_4_n20 : k_mhe_solve_r4_2_n20);
-        const char* const full_name = c.polish ? (c.L == 4 ? "k_mhe_solve_r4_4_n20_pol" : "k_mhe_solve_r4_2_n20_pol") : (c.L == 4 ? "k_mhe_solve_r4_4_n20" : "k_mhe_solve_r4_2_n20");
-        hipFuncAttributes fa;
-        size_t static_lds = 512;
-        if (hipFuncGetAttributes(&fa, (const void*)full) == hipSuccess) static_lds = fa.sharedSizeBytes;
-        if (lay.r4_fits(c.L, static_lds)) {
-            const long sf = 4L * prop.multiProcessorCount;
-            int gridf = (int)(sf < batch ? sf : batch);
-#ifdef DEKF_AB_KNOBS  // A/B builds only (tools/r4_check.py): another persistent grid
-            if (const char* ge = getenv("DEKF_DEBUG_R4_GRID")) { const int gv = atoi(ge); if (gv > 0 && gv <= batch) gridf = gv; }
-#endif
-            if (gridf > h->solve_grid) {
-                h->lds_solve_full = lay.r4_lds_bytes();
-                h->solve_grid_full = gridf;
-                h->solve_threads_full = DEKF_R4_THREADS;
-                h->solve_kernel_full = full;
-                h->solve_name_full = full_name;
-            }
-        }
-    }
-    if (!h->solve_kernel_full && !c.ft && c.N == 20 && (c.L == 4 || c.L == 2) && (cap == 0 || cap > per_cu)) {
-        const SolveFn full = c.polish ? (c.L == 4 ? k_mhe_solve_r3_4_n20_pol : k_mhe_solve_r3_2_n20_pol) : (c.L == 4 ? k_mhe_solve_r3_4_n20 : k_mhe_solve_r3_2_n20);
-        const char* const full_name = c.polish ? (c.L == 4 ? "k_mhe_solve_r3_4_n20_pol" : "k_mhe_solve_r3_2_n20_pol") : (c.L == 4 ? "k_mhe_solve_r3_4_n20" : "k_mhe_solve_r3_2_n20");
-        // the kernel's static LDS (reduction scratch of wave.h) counts against the same allocation as the dynamic part
-        hipFuncAttributes fa;
-        size_t static_lds = 512;
-        if (hipFuncGetAttributes(&fa, (const void*)full) == hipSuccess) static_lds = fa.sharedSizeBytes;
-        if (lay.r3_fits(c.L, static_lds)) {
-            h->lds_solve_full = lay.r3_lds_bytes();
-            int pcf = 1;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pcf, (const void*)full, DEKF_SOLVE_THREADS, h->lds_solve_full) != hipSuccess || pcf < 1)
-                pcf = 1;
-            if (pcf > DEKF_R3_WAVES) pcf = DEKF_R3_WAVES;  // the query over-reports: r3_fits has decided that DEKF_R3_WAVES fit
-            if (cap > 0 && pcf > cap) pcf = cap;
-            const long sf = (long)pcf * prop.multiProcessorCount;
-            h->solve_grid_full = (int)(sf < batch ? sf : batch);
-            // For EVERY batch since round 6 (it used to be only where the batch fills more slots than the two-workgroup kernel offers,
-            // "below that the row state would travel through the slab for no residency gained"): measured, the rows-in-registers
-            // kernel solves a full window in 0.278 ms against 0.350 ms even ALONE on its CU — 21-22 % less solve time at 64 ... 512
-            // instances (profiles/r06_r3_at_small_batches.txt).  The two-workgroup kernels keep the window-fill ticks, and full
-            // windows when the caller caps the residency at two.
-            bool take = pcf > per_cu;
-#ifdef DEKF_AB_KNOBS  // A/B builds only: the round-5 rule
-            if (getenv("DEKF_DEBUG_R3_ONLY_ABOVE_512")) take = pcf > per_cu && h->solve_grid_full > h->solve_grid;
-#endif
-            if (take) {
-                h->solve_kernel_full = full;
-                h->solve_name_full = full_name;
-            }
-        }
-    }
-#endif
-#ifndef DEKF_NO_RR
+    // Full windows (K == N) of some shapes run kernels of their own with more workgroups per CU: the first family whose rule takes it.
+    // Go1 / Cassie (N = 20): r3 for EVERY batch since round 6 (it used to be only where the batch fills more slots than the
+    // two-workgroup kernel offers, "below that the row state would travel through the slab for no residency gained"): measured, the
+    // rows-in-registers kernel solves a full window in 0.278 ms against 0.350 ms even ALONE on its CU — 21-22 % less solve time at
+    // 64 ... 512 instances (profiles/r06_r3_at_small_batches.txt).  The two-workgroup kernels keep the window-fill ticks, and full
+    // windows when the caller caps the residency at two; solve_workgroups_per_cu = 4 selects r4.
     // One-legged robots with long windows (PogoX: N = 100): the generic placement keeps 103 KB of iterates in LDS, one workgroup per
-    // CU.  Full windows run the kernel that keeps the row state in registers (mhe_admm_core.h: admm_chunk_rr) — 77 KB, two per CU —
-    // when the batch fills more slots than the generic kernel offers.
-    if (!h->solve_kernel_full && !c.ft && c.L == 1 && (cap == 0 || cap > per_cu)) {
-        const SolveFn full = c.polish ? k_mhe_solve_rr_1_pol : k_mhe_solve_rr_1;
-        const char* const full_name = c.polish ? "k_mhe_solve_rr_1_pol" : "k_mhe_solve_rr_1";
-        hipFuncAttributes fa;
-        size_t static_lds = 512;
-        if (hipFuncGetAttributes(&fa, (const void*)full) == hipSuccess) static_lds = fa.sharedSizeBytes;
-        if (lay.rr_fits(c.L, static_lds)) {
-            h->lds_solve_full = lay.rr_lds_bytes();
-            if (h->lds_solve_full > 64 * 1024)
-                (void)hipFuncSetAttribute((const void*)full, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_solve_full);
-            int pcf = 1;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pcf, (const void*)full, DEKF_SOLVE_THREADS, h->lds_solve_full) != hipSuccess || pcf < 1)
-                pcf = 1;
-            if (pcf > 2) pcf = 2;  // (rr_fits has decided that two fit; the kernel is compiled for two wavefronts per SIMD)
-            if (cap > 0 && pcf > cap) pcf = cap;
-            const long sf = (long)pcf * prop.multiProcessorCount;
-            h->solve_grid_full = (int)(sf < batch ? sf : batch);
-            // (for every batch since round 6: 10-13 % less solve time than the generic kernel at 32 ... 256 instances too,
-            // profiles/r06_r3_at_small_batches.txt)
-            bool take = pcf > per_cu;
-#ifdef DEKF_AB_KNOBS  // A/B builds only: the round-5 rule
-            if (getenv("DEKF_DEBUG_RR_ONLY_ABOVE_256")) take = pcf > per_cu && h->solve_grid_full > h->solve_grid;
-#endif
-            if (take) {
-                h->solve_kernel_full = full;
-                h->solve_name_full = full_name;
-            }
-        }
-    }
-#endif
+    // CU; rr keeps the row state in registers (mhe_admm_core.h: admm_chunk_rr) — 77 KB, two per CU — for every batch since round 6
+    // (10-13 % less solve time than the generic kernel at 32 ... 256 instances too, profiles/r06_r3_at_small_batches.txt).
+    const bool above_cap = cap == 0 || cap > per_cu;
+    const FullWindowFamily families[] = {
+        // four workgroups of three wavefronts per CU (round 6, admm_chunk_r4).  ADVICE (its own change): query the occupancy, LDS from prop
+        {SolveRole::r4, cap == 4, DEKF_R4_THREADS, lay.r4_lds_bytes(), &SolveLayout::r4_fits, 4, false, "DEKF_DEBUG_R4_GRID", nullptr},
+        {SolveRole::r3, above_cap, DEKF_SOLVE_THREADS, lay.r3_lds_bytes(), &SolveLayout::r3_fits, DEKF_R3_WAVES, true, nullptr, "DEKF_DEBUG_R3_ONLY_ABOVE_512"},
+        {SolveRole::rr, above_cap, DEKF_SOLVE_THREADS, lay.rr_lds_bytes(), &SolveLayout::rr_fits, 2, true, nullptr, "DEKF_DEBUG_RR_ONLY_ABOVE_256"},
+    };
+    for (const FullWindowFamily& f : families)
+        if (take_full_window(h, f, lay, per_cu, cap, prop.multiProcessorCount, batch)) break;
     const int solve_slots = h->solve_kernel_full && h->solve_grid_full > h->solve_grid ? h->solve_grid_full : h->solve_grid;
     Gws g;
     g.init(c.N, c.L, c.ft, h->c.gws_wt);

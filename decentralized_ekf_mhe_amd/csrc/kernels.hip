@@ -142,42 +142,16 @@ __global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_marginalize_early(De
 }
 #endif  // DEKF_MISC_KERNELS
 
-// three placements of the factor (mhe_solve_core.h: SolveLayout): _ll all in LDS (Go1, N = 20),
-// _lg LDS factor with the factor-time temporary in HBM (fewer legs), _gg factor streamed from HBM
-// One workgroup of DEKF_SOLVE_THREADS lanes (4 wavefronts, one per SIMD of the CU) per instance;
-// the leg count is a compile-time constant of each instantiation.  The second launch bound (2 waves
-// per SIMD) caps VGPR+AGPR at 256 so that TWO workgroups stay resident per CU — LDS allows exactly
-// two, and at 260 registers the kernel silently dropped to one (2x slower).
+// The solve kernels (solve_kernels.def).  One workgroup of DEKF_SOLVE_THREADS lanes (4 wavefronts, one per SIMD of the CU) per
+// instance; the leg count is a compile-time constant of each instantiation.  The second launch bound (2 waves per SIMD) caps
+// VGPR+AGPR at 256 so that TWO workgroups stay resident per CU — LDS allows exactly two, and at 260 registers the kernel silently
+// dropped to one (2x slower).
 // DEKF_SOLVE_MIN_WAVES: wavefronts per SIMD the generic instantiations are compiled for (2 -> 256 VGPRs; the
 // residency experiment in EXPERIMENTS.md II §4.4 builds them with 3 -> 168 VGPRs)
 #ifndef DEKF_SOLVE_MIN_WAVES
 #define DEKF_SOLVE_MIN_WAVES 2
 #endif
-// Which solve kernels a build carries: -DDEKF_KSET=<mask> (default: all).  Kernels outside the mask are empty stubs, so a library
-// built with a mask solves only the shapes of its kernels.  1: Go1 N = 20 (k_mhe_solve_ll_4_n20, k_mhe_solve_r3_4_n20) — what
-// -DDEKF_GO1_ONLY selects, the A/B builds of the benchmark shape (tools/ab_variants.sh; builds in seconds instead of minutes);
-// 2: Cassie N = 20 (k_mhe_solve_lg_2_n20, k_mhe_solve_r3_2_n20); 4 / 8 / 16 / 32: the generic kernels for 1 / 2 / 3 / 4 legs;
-// 64 / 128 / 256 / 512: the foot-position kernels (leg_odom_type 1) for 1 / 2 / 3 / 4 legs.  The bounds-checked diagnostic build
-// is compiled one mask at a time (tools/build_bounds.sh): with checked pointers one translation unit of everything takes hours.
-#ifndef DEKF_KSET
-#ifdef DEKF_GO1_ONLY
-#define DEKF_KSET 1
-#else
-#define DEKF_KSET 0x3FF
-#endif
-#endif
-// Every solve kernel exists twice: NAME, and NAME_pol with OSQP's polishing step behind the iterations (osqp.polish true; chosen
-// by dekf_create).  Two instantiations rather than a run-time branch: compiled into k_mhe_solve_r3_4_n20 the polishing code (a
-// second call site of the factorisation and of the iteration chunk) took its spilled VGPRs from 60 to 147.
-#ifdef DEKF_KSET_ONLY
-#define DEKF_STUB_KERNEL(NAME)
-#else
-#define DEKF_STUB_KERNEL(NAME)                                  \
-    __global__ void NAME(DevCfg, DevState, int, int, int) {}     \
-    __global__ void NAME##_pol(DevCfg, DevState, int, int, int) {}
-#endif
-#define DEKF_SOLVE_KERNEL_BODY_(NAME, WAVES, POLISH, ...) DEKF_SOLVE_KERNEL_BODY_T_(NAME, DEKF_SOLVE_THREADS, DEKF_QUEUE_LOOP, WAVES, POLISH, __VA_ARGS__)
-#define DEKF_SOLVE_KERNEL_BODY_T_(NAME, THREADS, LOOP, WAVES, POLISH, ...)                                                   \
+#define DEKF_SOLVE_BODY_(NAME, THREADS, WAVES, LOOP, POLISH, ...)                                                             \
     __global__ void __launch_bounds__(THREADS, WAVES) NAME(DevCfg c, DevState s, int kstart, int K, int gws_len) {            \
         extern __shared__ double lds[];                                                                                      \
         __shared__ int next_instance;                                                                                        \
@@ -187,118 +161,24 @@ __global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_marginalize_early(De
         solve_queue_leave(s);                                                                                                \
         DEKF_WG_TRACE_END                                                                                                    \
     }
-#ifdef DEKF_NO_POLISH_KERNELS  // (A/B and diagnostic builds: half the compile time; osqp.polish true is then refused by the stubs' owner, dekf_create)
-#define DEKF_SOLVE_KERNEL_BODY(NAME, WAVES, ...)            \
-    DEKF_SOLVE_KERNEL_BODY_(NAME, WAVES, false, __VA_ARGS__) \
-    __global__ void NAME##_pol(DevCfg, DevState, int, int, int) {}
-#else
-#define DEKF_SOLVE_KERNEL_BODY(NAME, WAVES, ...)            \
-    DEKF_SOLVE_KERNEL_BODY_(NAME, WAVES, false, __VA_ARGS__) \
-    DEKF_SOLVE_KERNEL_BODY_(NAME##_pol, WAVES, true, __VA_ARGS__)
-#endif
-#define DEKF_SOLVE_KERNEL_IF(BIT, NAME, WAVES, ...) DEKF_SOLVE_KERNEL_IF_(BIT, NAME, WAVES, __VA_ARGS__)
-#define DEKF_SOLVE_KERNEL_IF_(BIT, NAME, WAVES, ...) DEKF_SOLVE_KERNEL_SEL_##BIT(NAME, WAVES, __VA_ARGS__)
-// one selector per bit (the preprocessor cannot branch on an expression inside a macro body)
-#if DEKF_KSET & 1
-#define DEKF_SOLVE_KERNEL_SEL_0(NAME, WAVES, ...) DEKF_SOLVE_KERNEL_BODY(NAME, WAVES, __VA_ARGS__)
-#else
-#define DEKF_SOLVE_KERNEL_SEL_0(NAME, WAVES, ...) DEKF_STUB_KERNEL(NAME)
-#endif
-#if DEKF_KSET & 2
-#define DEKF_SOLVE_KERNEL_SEL_1(NAME, WAVES, ...) DEKF_SOLVE_KERNEL_BODY(NAME, WAVES, __VA_ARGS__)
-#else
-#define DEKF_SOLVE_KERNEL_SEL_1(NAME, WAVES, ...) DEKF_STUB_KERNEL(NAME)
-#endif
-#if DEKF_KSET & 4
-#define DEKF_SOLVE_KERNEL_SEL_2(NAME, WAVES, ...) DEKF_SOLVE_KERNEL_BODY(NAME, WAVES, __VA_ARGS__)
-#else
-#define DEKF_SOLVE_KERNEL_SEL_2(NAME, WAVES, ...) DEKF_STUB_KERNEL(NAME)
-#endif
-#if DEKF_KSET & 8
-#define DEKF_SOLVE_KERNEL_SEL_3(NAME, WAVES, ...) DEKF_SOLVE_KERNEL_BODY(NAME, WAVES, __VA_ARGS__)
-#else
-#define DEKF_SOLVE_KERNEL_SEL_3(NAME, WAVES, ...) DEKF_STUB_KERNEL(NAME)
-#endif
-#if DEKF_KSET & 16
-#define DEKF_SOLVE_KERNEL_SEL_4(NAME, WAVES, ...) DEKF_SOLVE_KERNEL_BODY(NAME, WAVES, __VA_ARGS__)
-#else
-#define DEKF_SOLVE_KERNEL_SEL_4(NAME, WAVES, ...) DEKF_STUB_KERNEL(NAME)
-#endif
-#if DEKF_KSET & 32
-#define DEKF_SOLVE_KERNEL_SEL_5(NAME, WAVES, ...) DEKF_SOLVE_KERNEL_BODY(NAME, WAVES, __VA_ARGS__)
-#else
-#define DEKF_SOLVE_KERNEL_SEL_5(NAME, WAVES, ...) DEKF_STUB_KERNEL(NAME)
-#endif
-#if DEKF_KSET & 64
-#define DEKF_SOLVE_KERNEL_SEL_6(NAME, WAVES, ...) DEKF_SOLVE_KERNEL_BODY(NAME, WAVES, __VA_ARGS__)
-#else
-#define DEKF_SOLVE_KERNEL_SEL_6(NAME, WAVES, ...) DEKF_STUB_KERNEL(NAME)
-#endif
-#if DEKF_KSET & 128
-#define DEKF_SOLVE_KERNEL_SEL_7(NAME, WAVES, ...) DEKF_SOLVE_KERNEL_BODY(NAME, WAVES, __VA_ARGS__)
-#else
-#define DEKF_SOLVE_KERNEL_SEL_7(NAME, WAVES, ...) DEKF_STUB_KERNEL(NAME)
-#endif
-#if DEKF_KSET & 256
-#define DEKF_SOLVE_KERNEL_SEL_8(NAME, WAVES, ...) DEKF_SOLVE_KERNEL_BODY(NAME, WAVES, __VA_ARGS__)
-#else
-#define DEKF_SOLVE_KERNEL_SEL_8(NAME, WAVES, ...) DEKF_STUB_KERNEL(NAME)
-#endif
-#if DEKF_KSET & 512
-#define DEKF_SOLVE_KERNEL_SEL_9(NAME, WAVES, ...) DEKF_SOLVE_KERNEL_BODY(NAME, WAVES, __VA_ARGS__)
-#else
-#define DEKF_SOLVE_KERNEL_SEL_9(NAME, WAVES, ...) DEKF_STUB_KERNEL(NAME)
-#endif
-// three placements of the factor per leg count: _ll all in LDS, _lg factor-time temporary in HBM, _gg factor streamed from HBM
-#define DEKF_SOLVE_KERNELS(BIT, LEGS)                                                                       \
-    DEKF_SOLVE_KERNEL_IF(BIT, k_mhe_solve_ll_##LEGS, DEKF_SOLVE_MIN_WAVES, LEGS, true, true)                \
-    DEKF_SOLVE_KERNEL_IF(BIT, k_mhe_solve_lg_##LEGS, DEKF_SOLVE_MIN_WAVES, LEGS, true, false)               \
-    DEKF_SOLVE_KERNEL_IF(BIT, k_mhe_solve_gg_##LEGS, DEKF_SOLVE_MIN_WAVES, LEGS, false, false)
-// the benchmark shape (Go1, N = 20) additionally with the horizon as a compile-time constant; its full windows run THREE
-// workgroups per CU (mhe_admm_core.h, admm_chunk_r3: row state in registers, 168 VGPRs); the window-fill ticks (K < N) keep the
-// two-workgroup kernel
-DEKF_SOLVE_KERNEL_IF(0, k_mhe_solve_ll_4_n20, 2, 4, true, true, 20)
-DEKF_SOLVE_KERNEL_IF(0, k_mhe_solve_r3_4_n20, DEKF_R3_WAVES, 4, true, true, 20, 0, true)
-// the same full windows on workgroups of THREE wavefronts at FOUR per CU (round 6; mhe_admm_core.h: admm_chunk_r4, SolveLayout::r4_*)
+#define DEKF_SOLVE_STUB_(NAME) __global__ void NAME(DevCfg, DevState, int, int, int) {}
+// a kernel of the build's sets and its polishing twin (-DDEKF_NO_POLISH_KERNELS, A/B and diagnostic builds: an empty twin — half the
+// compile time; osqp.polish true is then refused by dekf_create)
 #ifdef DEKF_NO_POLISH_KERNELS
-#define DEKF_SOLVE_KERNEL_R4(NAME, ...)                                              \
-    DEKF_SOLVE_KERNEL_BODY_T_(NAME, DEKF_R4_THREADS, DEKF_QUEUE_LOOP_DYNAMIC, DEKF_R3_WAVES, false, __VA_ARGS__) \
-    __global__ void NAME##_pol(DevCfg, DevState, int, int, int) {}
+#define DEKF_SOLVE_KERNEL(NAME, ROLE, THREADS, WAVES, LOOP, ...) \
+    DEKF_SOLVE_BODY_(NAME, THREADS, WAVES, LOOP, false, __VA_ARGS__) DEKF_SOLVE_STUB_(NAME##_pol)
 #else
-#define DEKF_SOLVE_KERNEL_R4(NAME, ...)                                              \
-    DEKF_SOLVE_KERNEL_BODY_T_(NAME, DEKF_R4_THREADS, DEKF_QUEUE_LOOP_DYNAMIC, DEKF_R3_WAVES, false, __VA_ARGS__) \
-    DEKF_SOLVE_KERNEL_BODY_T_(NAME##_pol, DEKF_R4_THREADS, DEKF_QUEUE_LOOP_DYNAMIC, DEKF_R3_WAVES, true, __VA_ARGS__)
+#define DEKF_SOLVE_KERNEL(NAME, ROLE, THREADS, WAVES, LOOP, ...) \
+    DEKF_SOLVE_BODY_(NAME, THREADS, WAVES, LOOP, false, __VA_ARGS__) DEKF_SOLVE_BODY_(NAME##_pol, THREADS, WAVES, LOOP, true, __VA_ARGS__)
 #endif
-#if DEKF_KSET & 1
-DEKF_SOLVE_KERNEL_R4(k_mhe_solve_r4_4_n20, 4, true, false, 20, 0, true)
+// a kernel outside the sets: empty stubs, so a library built with a mask solves only the shapes of its kernels; none in the
+// product build's per-set units (-DDEKF_KSET_ONLY: another unit defines it)
+#ifdef DEKF_KSET_ONLY
+#define DEKF_SOLVE_KERNEL_OFF(...)
 #else
-DEKF_STUB_KERNEL(k_mhe_solve_r4_4_n20)
+#define DEKF_SOLVE_KERNEL_OFF(NAME, ...) DEKF_SOLVE_STUB_(NAME) DEKF_SOLVE_STUB_(NAME##_pol)
 #endif
-#if DEKF_KSET & 2
-DEKF_SOLVE_KERNEL_R4(k_mhe_solve_r4_2_n20, 2, true, false, 20, 0, true)
-#else
-DEKF_STUB_KERNEL(k_mhe_solve_r4_2_n20)
-#endif
-// Cassie (2 legs, N = 20; its factor-time temporary does not fit next to the vectors: _lg placement)
-DEKF_SOLVE_KERNEL_IF(1, k_mhe_solve_lg_2_n20, 2, 2, true, false, 20)
-DEKF_SOLVE_KERNEL_IF(1, k_mhe_solve_r3_2_n20, DEKF_R3_WAVES, 2, true, true, 20, 0, true)
-DEKF_SOLVE_KERNELS(2, 1)
-// one leg, long windows (PogoX, N = 100): full windows with the row state in registers at a run-time horizon, factor in the slab,
-// TWO workgroups per CU instead of the one that the generic placement's 103 KB of iterates allow (mhe_admm_core.h: admm_chunk_rr)
-DEKF_SOLVE_KERNEL_IF(2, k_mhe_solve_rr_1, 2, 1, false, false, 0, 0, true)
-DEKF_SOLVE_KERNELS(3, 2)
-DEKF_SOLVE_KERNELS(4, 3)
-DEKF_SOLVE_KERNELS(5, 4)
-// leg_odom_type 1: the foot positions are states (9 + 3 LEGS per window step, 21 for Go1).  Two placements: factor in
-// LDS with the factor-time temporary in HBM (short windows), factor streamed from the workgroup's HBM slab (Go1, N = 20:
-// S^-1 and W alone are 141 KB).
-#define DEKF_SOLVE_KERNELS_FOOT(BIT, LEGS)                                                                         \
-    DEKF_SOLVE_KERNEL_IF(BIT, k_mhe_solve_foot_lg_##LEGS, DEKF_SOLVE_MIN_WAVES, LEGS, true, false, 0, 1)           \
-    DEKF_SOLVE_KERNEL_IF(BIT, k_mhe_solve_foot_gg_##LEGS, DEKF_SOLVE_MIN_WAVES, LEGS, false, false, 0, 1)
-DEKF_SOLVE_KERNELS_FOOT(6, 1)
-DEKF_SOLVE_KERNELS_FOOT(7, 2)
-DEKF_SOLVE_KERNELS_FOOT(8, 3)
-DEKF_SOLVE_KERNELS_FOOT(9, 4)
+#include "solve_kernels.def"
 
 #if DEKF_MISC_KERNELS
 __global__ void k_gap() {}

@@ -54,7 +54,7 @@ def parse_usage(text):
 
 
 def _sources_mtime():
-    return max(os.path.getmtime(os.path.join(CSRC, f)) for f in os.listdir(CSRC) if f.endswith((".h", ".hip", ".sh")))
+    return max(os.path.getmtime(os.path.join(CSRC, f)) for f in os.listdir(CSRC) if f.endswith((".h", ".hip", ".def", ".sh")))
 
 
 def _compile_sets(masks):
