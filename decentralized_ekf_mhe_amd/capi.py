@@ -45,6 +45,8 @@ PROTOTYPES = {
     "dekf_get_solver_info": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
     "dekf_get_polish_status": (C.c_int, [_vp, _vp, C.c_int]),
     "dekf_get_kf_cov": (C.c_int, [_vp, _vp, C.c_int]),
+    "dekf_set_warm_start": (C.c_int, [_vp, C.c_int]),
+    "dekf_get_warm_status": (C.c_int, [_vp, _vp, C.c_int]),
     "dekf_timing_enable": (C.c_int, [_vp, C.c_int]),
     "dekf_timing_read": (C.c_int, [_vp, _dp, _ip]),
     "dekf_launch_info": (C.c_int, [_vp, _ip, _ip, _dp]),

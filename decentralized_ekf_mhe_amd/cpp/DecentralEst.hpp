@@ -98,6 +98,9 @@ struct robot_params {
     bool verbose_ = false, adaptRho_ = true, polish_ = false;
     int maxQPIter_ = 4000;
     double realtiveTol_ = 1e-6, absTol_ = 1e-6, primTol_ = 1e-6, dualTol_ = 1e-6, timeLimit_ = 0.0028;
+    // OSQP's warm_start (DecentralEst.cpp:204 sets it; the reference's solver is rebuilt every tick, so it never takes effect there):
+    // full-window solves start from the previous tick's shifted solution (dekf_set_warm_start; MHE only)
+    bool warmStart_ = false;
 };
 
 // ---- DecentralEst.hpp:65-94 ----------------------------------------------------------------
@@ -181,6 +184,7 @@ class DecentralizedEstimation {
         x_MHE_.resize(dim_state_);
         x_KF_.resize(dim_state_);
         C_KF_ = MatrixXd(dim_state_, dim_state_);
+        if (params->warmStart_ && prm_.est_type == 0) dekf_shim::check(dekf_set_warm_start(h_, 1));
         latch();
         dekf_shim::check(dekf_initialize(h_));
         fetch();

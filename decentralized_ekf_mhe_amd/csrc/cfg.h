@@ -67,6 +67,22 @@ struct DevCfg {
     // EKF (orien_ekf.cpp:13-31)
     double ekf_dt, ekf_Cgyro[3], ekf_Caccel[3], ekf_Cvo[4], ekf_P0[4], ekf_q0[4];
     int ekf_hist;
+    int warm;  // dekf_set_warm_start: full-window solves start from the previous tick's shifted iterate (DevState::warm); 0: cold
+};
+
+// The warm store of one instance (dekf_set_warm_start, [B][len] doubles): the UNSCALED ADMM iterate of the instance's last
+// full-window solve and its final rho, in the solver's own order — x blocks [N][ns] | slack x by row [m_pad] | y by row [m_pad] |
+// rho.  Every variable is an x-block entry or the slack of exactly one row (n = N ns + m), so that is the whole primal iterate.
+struct WarmLayout {
+    int X, XS, Y, RHO, len;
+    DEKF_HD void init(int N, int ns, int nm) {
+        const int m_pad = N * (nm + ns + 3);
+        X = 0;
+        XS = N * ns;
+        Y = XS + m_pad;
+        RHO = Y + m_pad;
+        len = RHO + 1;
+    }
 };
 
 // argument block of k_latch4: up to four double arrays copied by one launch; end[i] = running element count
@@ -200,6 +216,12 @@ struct DevState {
     int* polish_status;  // 0 polishing off / not reached, 1 polished point accepted, -1 rejected (OSQP's status_polish)
     double *pri_res, *dua_res;
     double* prof;  // [B][DEKF_PROF_SLOTS] section cycles, written by the diagnostic (-DDEKF_PROFILE) build only
+    // warm start (DevCfg::warm; allocated by dekf_set_warm_start, null otherwise): the store [B][WarmLayout::len]; warm_tag[b] = the step T
+    // whose solve wrote a valid store (-1: none — window-fill tick, failed or non-finite solve, dekf_reset); warm_used[b] = 1 when the last
+    // solve started from it
+    double* warm = nullptr;
+    int* warm_tag = nullptr;
+    int* warm_used = nullptr;
 };
 
 }  // namespace dekf

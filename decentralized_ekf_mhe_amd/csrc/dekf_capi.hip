@@ -25,7 +25,9 @@ __global__ void k_mhe_marginalize_early(DevCfg c, DevState s, int T);
 // every solve kernel and its twin with OSQP's polishing step (solve_kernels.def)
 #define DEKF_SOLVE_KERNEL(NAME, ...)                                                   \
     __global__ void NAME(DevCfg c, DevState s, int kstart, int K, int gws_len);        \
-    __global__ void NAME##_pol(DevCfg c, DevState s, int kstart, int K, int gws_len);
+    __global__ void NAME##_pol(DevCfg c, DevState s, int kstart, int K, int gws_len);  \
+    __global__ void NAME##_warm(DevCfg c, DevState s, int kstart, int K, int gws_len); \
+    __global__ void NAME##_warm_pol(DevCfg c, DevState s, int kstart, int K, int gws_len);
 #include "solve_kernels.def"
 __global__ void k_gap();
 __global__ void k_kf_initialize(DevCfg c, DevState s);
@@ -46,6 +48,7 @@ struct RcclApi;  // rccl_dyn.h
 }  // namespace
 #include "rccl_dyn.h"
 
+namespace { struct SolveKernel; }
 struct dekf_handle_s {
     dekf_params prm;
     DevCfg c;
@@ -65,6 +68,7 @@ struct dekf_handle_s {
     int solve_threads_full = DEKF_SOLVE_THREADS;  // (the four-per-CU kernels: DEKF_R4_THREADS)
     size_t lds_solve_full = 0;
     const char *solve_name = nullptr, *solve_name_full = nullptr;  // kernel symbols, for dekf_solve_kernel_name
+    const SolveKernel* solve_entry_full = nullptr;  // the catalogue's row of solve_kernel_full (its warm twin: dekf_set_warm_start)
     size_t lds_solve = 0, lds_asm = 0, lds_kf = 0;
     int ekf_count = 0, pushes = 0, next_T = 0;
     bool initialized = false;
@@ -129,11 +133,16 @@ struct SolveKernel {
     int legs, nfix;  // solve_window_t's L and NFIX (0: run-time horizon)
     SolveFn fn, fn_pol;
     const char *name, *name_pol;
+    bool warm_twin;  // a warm handle launches fn_warm / fn_warm_pol instead (solve_kernels.def: DEKF_WARM_TWIN_<role>)
+    SolveFn fn_warm, fn_warm_pol;
+    const char *name_warm, *name_warm_pol;
 };
 #define DEKF_LEGS_(L, ...) L
 #define DEKF_NFIX_(L, FACTOR_LDS, PA_LDS, NFIX, ...) NFIX
-#define DEKF_SOLVE_KERNEL(NAME, ROLE, THREADS, WAVES, LOOP, ...) \
-    {SolveRole::ROLE, DEKF_LEGS_(__VA_ARGS__), DEKF_NFIX_(__VA_ARGS__, 0, 0), NAME, NAME##_pol, #NAME, #NAME "_pol"},
+#define DEKF_WARM_TWIN_OF_(ROLE) DEKF_WARM_TWIN_##ROLE
+#define DEKF_SOLVE_KERNEL(NAME, ROLE, THREADS, WAVES, LOOP, ...)                                                   \
+    {SolveRole::ROLE, DEKF_LEGS_(__VA_ARGS__), DEKF_NFIX_(__VA_ARGS__, 0, 0), NAME, NAME##_pol, #NAME, #NAME "_pol", \
+     DEKF_WARM_TWIN_OF_(ROLE) != 0, NAME##_warm, NAME##_warm_pol, #NAME "_warm", #NAME "_warm_pol"},
 const SolveKernel solve_kernels[] = {
 #include "solve_kernels.def"
 };
@@ -192,6 +201,9 @@ bool take_full_window(dekf_handle h, const FullWindowFamily& f, const SolveLayou
     if (!take) return false;
     h->solve_kernel_full = fn;
     h->solve_name_full = h->c.polish ? k->name_pol : k->name;
+    h->solve_entry_full = k;
+    if (k->warm_twin && f.lds > 64 * 1024)
+        (void)hipFuncSetAttribute((const void*)(h->c.polish ? k->fn_warm_pol : k->fn_warm), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds);
     h->solve_grid_full = grid;
     h->solve_threads_full = f.threads;
     h->lds_solve_full = f.lds;
@@ -753,6 +765,55 @@ dekf_status dekf_get_polish_status(dekf_handle h, int* polish_status, dekf_mem w
     dekf_status st;
     if ((st = await_results(h))) return st;
     if ((st = fetch(h, polish_status, h->sp[h->last_par].polish_status, (size_t)h->c.B * 4, where))) return st;
+    if (where == DEKF_HOST) HIPCHK(hipStreamSynchronize(h->stream));
+    return DEKF_OK;
+}
+
+dekf_status dekf_set_warm_start(dekf_handle h, int on) {
+    if (!h) return fail(DEKF_ERR_INVALID, "null handle");
+    if (on != 0 && on != 1) return fail(DEKF_ERR_INVALID, "dekf_set_warm_start: on must be 0 or 1");
+    if (h->c.est_type != 0) return fail(DEKF_ERR_INVALID, "warm start is an MHE setting: this is a KF handle (est_type 1)");
+    if (h->pipelined) return fail(DEKF_ERR_INVALID, "warm start cannot be combined with solve_pipeline = 1");
+    if (h->initialized) return fail(DEKF_ERR_ORDER, "dekf_set_warm_start is allowed before dekf_initialize or right after dekf_reset");
+    HIPCHK(hipSetDevice(h->device));
+    if (on && !h->s.warm) {
+        WarmLayout wl;
+        wl.init(h->c.N, h->c.ns, h->c.nm);
+        const size_t B = (size_t)h->c.B;
+        double* w = nullptr;
+        int* t = nullptr;
+        HIPCHK(hipMalloc(&w, B * wl.len * sizeof(double)));
+        h->blocks.push_back(w);
+        HIPCHK(hipMalloc(&t, 2 * B * sizeof(int)));
+        h->blocks.push_back(t);
+        HIPCHK(hipMemsetAsync(t, 0xff, B * sizeof(int), h->stream));  // tags -1: no store is valid yet
+        HIPCHK(hipMemsetAsync(t + B, 0, B * sizeof(int), h->stream));
+        h->s.warm = w;
+        h->s.warm_tag = t;
+        h->s.warm_used = t + B;
+        h->sp[0] = h->s;
+        h->sp[1] = h->s;  // (not pipelined)
+    }
+    h->c.warm = on;
+    // a full-window kernel whose register budget left the warm start's code out: its twin carries it
+    if (const SolveKernel* k = h->solve_entry_full; k && k->warm_twin) {
+        const bool pol = h->c.polish != 0;
+        h->solve_kernel_full = on ? (pol ? k->fn_warm_pol : k->fn_warm) : (pol ? k->fn_pol : k->fn);
+        h->solve_name_full = on ? (pol ? k->name_warm_pol : k->name_warm) : (pol ? k->name_pol : k->name);
+    }
+    return DEKF_OK;
+}
+
+dekf_status dekf_get_warm_status(dekf_handle h, int* warm, dekf_mem where) {
+    if (!h || !warm) return fail(DEKF_ERR_INVALID, "null argument");
+    const size_t n = (size_t)h->c.B * sizeof(int);
+    if (!h->s.warm_used) {  // never enabled: every solve started cold
+        if (where == DEKF_HOST) std::memset(warm, 0, n);
+        else HIPCHK(hipMemsetAsync(warm, 0, n, h->stream));
+        return DEKF_OK;
+    }
+    dekf_status st;
+    if ((st = fetch(h, warm, h->s.warm_used, n, where))) return st;
     if (where == DEKF_HOST) HIPCHK(hipStreamSynchronize(h->stream));
     return DEKF_OK;
 }

@@ -151,32 +151,44 @@ __global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_marginalize_early(De
 #ifndef DEKF_SOLVE_MIN_WAVES
 #define DEKF_SOLVE_MIN_WAVES 2
 #endif
-#define DEKF_SOLVE_BODY_(NAME, THREADS, WAVES, LOOP, POLISH, ...)                                                             \
+// ON: false for an empty body (a warm twin the row's role does not have, solve_kernels.def: DEKF_WARM_TWIN_*)
+#define DEKF_SOLVE_BODY_(NAME, THREADS, WAVES, LOOP, ON, POLISH, WARM, ...)                                                   \
     __global__ void __launch_bounds__(THREADS, WAVES) NAME(DevCfg c, DevState s, int kstart, int K, int gws_len) {            \
+        if constexpr (ON) {                                                                                                  \
         extern __shared__ double lds[];                                                                                      \
         __shared__ int next_instance;                                                                                        \
         double* gws = s.gws + (size_t)blockIdx.x * gws_len;                                                                  \
         DEKF_WG_TRACE_BEGIN                                                                                                  \
-        LOOP(solve_window_t<POLISH, __VA_ARGS__>(c, s, b, kstart, K, lds, gws))                                              \
+        LOOP(SolveEntry<POLISH, WARM>::template run<__VA_ARGS__>(c, s, b, kstart, K, lds, gws))                              \
         solve_queue_leave(s);                                                                                                \
         DEKF_WG_TRACE_END                                                                                                    \
+        }                                                                                                                    \
     }
 #define DEKF_SOLVE_STUB_(NAME) __global__ void NAME(DevCfg, DevState, int, int, int) {}
-// a kernel of the build's sets and its polishing twin (-DDEKF_NO_POLISH_KERNELS, A/B and diagnostic builds: an empty twin — half the
-// compile time; osqp.polish true is then refused by dekf_create)
+// a kernel of the build's sets, its polishing twin (-DDEKF_NO_POLISH_KERNELS, A/B and diagnostic builds: an empty twin — half the
+// compile time; osqp.polish true is then refused by dekf_create) and, for the roles with DEKF_WARM_TWIN_<role> 1, the warm twins
+// NAME_warm / NAME_warm_pol: NAME is then compiled without the warm start's code (empty stubs for the other roles, whose kernels
+// carry it behind a run-time branch)
+#define DEKF_WARM_TWIN_(ROLE) DEKF_WARM_TWIN_##ROLE
 #ifdef DEKF_NO_POLISH_KERNELS
-#define DEKF_SOLVE_KERNEL(NAME, ROLE, THREADS, WAVES, LOOP, ...) \
-    DEKF_SOLVE_BODY_(NAME, THREADS, WAVES, LOOP, false, __VA_ARGS__) DEKF_SOLVE_STUB_(NAME##_pol)
+#define DEKF_SOLVE_KERNEL(NAME, ROLE, THREADS, WAVES, LOOP, ...)                                                              \
+    DEKF_SOLVE_BODY_(NAME, THREADS, WAVES, LOOP, true, false, !DEKF_WARM_TWIN_(ROLE), __VA_ARGS__)                            \
+    DEKF_SOLVE_STUB_(NAME##_pol)                                                                                             \
+    DEKF_SOLVE_BODY_(NAME##_warm, THREADS, WAVES, LOOP, DEKF_WARM_TWIN_(ROLE), false, true, __VA_ARGS__)                      \
+    DEKF_SOLVE_STUB_(NAME##_warm_pol)
 #else
-#define DEKF_SOLVE_KERNEL(NAME, ROLE, THREADS, WAVES, LOOP, ...) \
-    DEKF_SOLVE_BODY_(NAME, THREADS, WAVES, LOOP, false, __VA_ARGS__) DEKF_SOLVE_BODY_(NAME##_pol, THREADS, WAVES, LOOP, true, __VA_ARGS__)
+#define DEKF_SOLVE_KERNEL(NAME, ROLE, THREADS, WAVES, LOOP, ...)                                                              \
+    DEKF_SOLVE_BODY_(NAME, THREADS, WAVES, LOOP, true, false, !DEKF_WARM_TWIN_(ROLE), __VA_ARGS__)                            \
+    DEKF_SOLVE_BODY_(NAME##_pol, THREADS, WAVES, LOOP, true, true, !DEKF_WARM_TWIN_(ROLE), __VA_ARGS__)                       \
+    DEKF_SOLVE_BODY_(NAME##_warm, THREADS, WAVES, LOOP, DEKF_WARM_TWIN_(ROLE), false, true, __VA_ARGS__)                      \
+    DEKF_SOLVE_BODY_(NAME##_warm_pol, THREADS, WAVES, LOOP, DEKF_WARM_TWIN_(ROLE), true, true, __VA_ARGS__)
 #endif
 // a kernel outside the sets: empty stubs, so a library built with a mask solves only the shapes of its kernels; none in the
 // product build's per-set units (-DDEKF_KSET_ONLY: another unit defines it)
 #ifdef DEKF_KSET_ONLY
 #define DEKF_SOLVE_KERNEL_OFF(...)
 #else
-#define DEKF_SOLVE_KERNEL_OFF(NAME, ...) DEKF_SOLVE_STUB_(NAME) DEKF_SOLVE_STUB_(NAME##_pol)
+#define DEKF_SOLVE_KERNEL_OFF(NAME, ...) DEKF_SOLVE_STUB_(NAME) DEKF_SOLVE_STUB_(NAME##_pol) DEKF_SOLVE_STUB_(NAME##_warm) DEKF_SOLVE_STUB_(NAME##_warm_pol)
 #endif
 #include "solve_kernels.def"
 
@@ -256,6 +268,10 @@ __global__ void k_reset_state(DevCfg c, DevState s) {
     s.vo_ins_idx[b] = 0;
     s.vo_ins_dtime[b] = 0;
     s.marg_tag[b] = -1;
+    if (s.warm_tag) {  // (dekf_reset: no solve starts warm from before it)
+        s.warm_tag[b] = -1;
+        s.warm_used[b] = 0;
+    }
 }
 
 #endif  // DEKF_MISC_KERNELS

@@ -1767,6 +1767,96 @@ DEKF_FN void r4_fill_dxb(Q& q) {
     wfor(q.K * NS, [&](int e) { const int k = e / NS, j = e - NS * k; q.Dxb[e] = q.D[k * SV + j]; });
 }
 
+// ---------------------------------------------------------------- warm start (dekf_set_warm_start)
+// The previous tick's iterate, SHIFTED by one window block: variable block k and row block k of this window
+// take block k + 1 of the last one.  The entering variables make the entering equality rows hold exactly — x_{K-1} through this
+// tick's Dyn rows of step K - 2 with w = 0, v_{K-1} from this tick's Meas rows — the entering w and c are 0, the entering duals 0.
+// z is A x (osqp_warm_start) on the VO rows; an equality row starts on its bound, which is where the first projection puts it and what
+// the rows-in-registers kernels restart from (RowRegsT: z of an equality block is not state).  The store is unscaled (x = D x^,
+// y = E y^ / c); this tick's Ruiz D, E and c scale it back.  R3 families: into xb and the row stash (sx, sy, sz — the caller says
+// where: the three-workgroup kernel's stash is overwritten by the factorisation, so it goes through the slab); the others: x, z, y.
+// Every product that meets a sum is an explicit fma: the families must see the same bits (the compiler contracts freely otherwise).
+template <class Q>
+DEKF_FN void warm_load(Q& q, cdptr w, const WarmLayout& wl, dptr sxo, dptr syo, dptr szo) {
+    constexpr int NS = Q::NS, NM = 3 * Q::LEGS;
+    const int K = q.K, m = q.m;
+    cdptr wx = w + wl.X, ws = w + wl.XS, wy = w + wl.Y;
+    auto xlast = [&](int j) {  // x_{K-1}[j]: A_dyn x_{K-2} - x_{K-1} - w_{K-2} = l with w = 0
+        double acc = 0.0;
+        for (int i = 0; i < NS; ++i) acc = fma(q.adyn(K - 2, j, i), wx[NS * (K - 1) + i], acc);
+        double lb, ub;
+        q.bounds(K - 2, 1, j, lb, ub);
+        return acc - lb;
+    };
+    wfor(K * NS + m, [&](int e) {
+        if (e < K * NS) {
+            const int k = e / NS, j = e - NS * k;
+            const double xv = (k < K - 1 ? wx[e + NS] : xlast(j)) / q.D[q.ix.x(k, j)];
+            if constexpr (Q::R3) q.xb[e] = xv;
+            else q.x[q.ix.x(k, j)] = xv;
+            return;
+        }
+        const int r = e - K * NS;
+        int k, kind, o;
+        q.dec_row(r, k, kind, o);
+        const bool enter = kind == 0 ? k == K - 1 : k == K - 2;
+        const int ro = r + (kind == 0 ? NM : (kind == 1 ? NS : 3));  // the same row one block later, in the previous window
+        double su = 0.0, yu = 0.0;
+        if (!enter) { su = ws[ro]; yu = wy[ro]; }
+        else if (kind == 0) {  // v_{K-1}: A_meas x_{K-1} - v_{K-1} = l
+            double lb, ub;
+            q.bounds(k, 0, o, lb, ub);
+            const int a = o % 3;
+            su = (Q::FOOT ? xlast(9 + o) - xlast(a) : xlast(3 + a)) - lb;
+        }
+        const int sv = q.row_slack(k, kind, o);
+        const double xs = su / q.D[sv], yv = q.cc * yu / q.E[r];
+        double zv = q.lo[r];
+        if (kind == 2) {  // VO row: p_k - p_{k+1} - c_k
+            const double p0 = wx[NS * (k + 1) + o], p1 = k + 1 < K - 1 ? wx[NS * (k + 2) + o] : xlast(o);
+            zv = q.E[r] * (p0 - p1 - su);
+        }
+        if constexpr (Q::R3) {
+            sxo[r] = xs;
+            syo[r] = yv;
+            if (kind == 2) szo[r - q.ix.rvb] = zv;
+        } else {
+            q.x[sv] = xs;
+            q.y[r] = yv;
+            q.z[r] = zv;
+        }
+    });
+}
+// the iterate after the last iteration, unscaled, and the final rho into the store; false if any of it is not finite
+template <class Q>
+DEKF_FN bool warm_save(Q& q, dptr w, const WarmLayout& wl, double cinv) {
+    constexpr int NS = Q::NS;
+    const int K = q.K, m = q.m;
+    const double bad = wred_max(K * NS + m + 1, [&](int e) -> double {
+        double v0 = 0.0, v1 = 0.0;
+        if (e < K * NS) {
+            const int k = e / NS, j = e - NS * k, xi = q.ix.x(k, j);
+            if constexpr (Q::R3) v0 = q.D[xi] * q.xb[e];
+            else v0 = q.D[xi] * q.x[xi];
+            w[wl.X + e] = v0;
+        } else if (e < K * NS + m) {
+            const int r = e - K * NS;
+            int k, kind, o;
+            q.dec_row(r, k, kind, o);
+            const int sv = q.row_slack(k, kind, o);
+            if constexpr (Q::R3) { v0 = q.D[sv] * q.sx[r]; v1 = q.E[r] * q.sy[r] * cinv; }
+            else { v0 = q.D[sv] * q.x[sv]; v1 = q.E[r] * q.y[r] * cinv; }
+            w[wl.XS + r] = v0;
+            w[wl.Y + r] = v1;
+        } else {
+            v0 = q.rho;
+            w[wl.RHO] = v0;
+        }
+        return fabs(v0) <= 1e300 && fabs(v1) <= 1e300 ? 0.0 : 1.0;
+    });
+    return bad == 0.0;
+}
+
 struct SolveInfo {
     int iters, status, rho_updates;
     double pri_res, dua_res, rho;
@@ -1777,7 +1867,9 @@ struct SolveInfo {
 // osqp_setup + osqp_solve + extraction.  window = steps kstart .. kstart+K-1 (newest = T).
 // FACTOR_LDS / PA_LDS are compile-time so that every pointer has a provable address space
 // (ds_read/ds_write instead of flat_load) — see SolveLayout::factor_in_lds / pa_in_lds.
-template <bool POLISH, int L, bool FACTOR_LDS, bool PA_LDS, int NFIX = 0, int FT = 0, bool R3 = false>
+// WARM: the warm start's entry and exit are compiled in (run-time branch on DevCfg::warm); false only for the kernels whose register
+// budget the extra code moves — they get a twin with it (solve_kernels.def: NAME_warm), and a warm handle launches that twin.
+template <bool POLISH, int L, bool FACTOR_LDS, bool PA_LDS, int NFIX = 0, int FT = 0, bool R3 = false, bool WARM = true>
 DEKF_FN SolveInfo solve_window_t(const DevCfg& c, const DevState& s, int b, int kstart, int K, dptr lds, dptr gws) {
     // NFIX != 0: the horizon is a compile-time constant, so every LDS array sits at a constant offset
     // (folded into the ds_read/ds_write immediates instead of living in scalar registers)
@@ -2013,6 +2105,14 @@ DEKF_FN SolveInfo solve_window_t(const DevCfg& c, const DevState& s, int b, int 
     else { wfor(n + m, [&](int e) { if (e < n) q.D[e] = 1.0; else q.E[e - n] = 1.0; }); }
     }
     DEKF_PROF_MARK(q, 0);
+    // warm start: a full window whose previous tick wrote a valid store (decided per instance; dekf_set_warm_start).  Nothing of it
+    // stays live across the iterations: the exit below derives the store's address again.
+    int warm_tag = WARM && c.warm && K == NH ? s.warm_tag[b] : -1;
+#if DEKF_DEVICE_BUILD
+    warm_tag = __builtin_amdgcn_readfirstlane(warm_tag);
+#endif
+    const bool warm = warm_tag >= 0 && warm_tag == kstart + K - 2;
+    if (WARM && c.warm && DEKF_LANE() == 0) s.warm_used[b] = warm ? 1 : 0;
     q.rho = uni_pin(c.rho0c);
     // scaled bounds, cold start
     dptr x = q.x, z = q.z, y = q.y, at = q.at;
@@ -2031,9 +2131,28 @@ DEKF_FN SolveInfo solve_window_t(const DevCfg& c, const DevState& s, int b, int 
             at[r] = 0.0;  // u = rho z - y of the cold start
         }
     });
+    if (warm) {  // rho of the previous solve (the first factorisation uses it) and the shifted iterate
+        WarmLayout wl;
+        wl.init(NH, NS, IdxT<L, FT>::nm);
+        const cdptr wst = DEKF_CSPAN(s.warm + (size_t)wl.len * b, wl.len);
+        q.rho = uni_pin(dmin(dmax(wst[wl.RHO], RHO_MIN), RHO_MAX));
+        if constexpr (R3 && FACTOR_LDS && !R4) warm_load(q, wst, wl, q.x, q.y, q.z);  // (the stash is factor-time scratch: via the slab)
+        else warm_load(q, wst, wl, q.sx, q.sy, q.sz);
+        if constexpr (R3) q.cold = false;
+    }
     DEKF_PROF_MARK(q, 19);
     bool ok = solve_factor(q);
     if constexpr (R4) r4_fill_dxb(q);
+    if constexpr (R3 && FACTOR_LDS && !R4) {
+        if (warm) {
+            const int mp = lay.m_pad, nz = 3 * NH;
+            wfor(2 * mp + nz, [&](int e) {
+                if (e < mp) q.sx[e] = q.x[e];
+                else if (e < 2 * mp) q.sy[e - mp] = q.y[e - mp];
+                else q.sz[e - 2 * mp] = q.z[e - 2 * mp];
+            });
+        }
+    }
     // scaled linear cost on x_0 (LDS copy for the per-lane look-ups)
     wfor(NS, [&](int j) { q.tmp[TM::QSL + j] = q.cc * q.D[ix.x(0, j)] * q.np[j]; });
     const double sigma = c.sigma, alpha = c.alpha;
@@ -2047,7 +2166,7 @@ DEKF_FN SolveInfo solve_window_t(const DevCfg& c, const DevState& s, int b, int 
     if (DEKF_LANE() == 0) info.next_fetch = atomicAdd(s.queue, 1);
 #endif
     if constexpr (!R3) {  // (R3: the first chunk's load of the row blocks is the restart)
-    if (ok) phase_rows<true>(q, alpha, sigma);  // cold start: cf, t = 0, w = 0 (the factorisation scratch aliased xt | zt | at)
+    if (ok) phase_rows<true>(q, alpha, sigma);  // cold start: cf, t = 0, w = 0 (the factorisation scratch aliased xt | zt | at); warm: from x, z, y
     }
     DEKF_PROF_MARK(q, 1);
     while (ok && !done && iter < c.max_iter) {
@@ -2128,6 +2247,12 @@ DEKF_FN SolveInfo solve_window_t(const DevCfg& c, const DevState& s, int b, int 
     }
     info.iters = iter;
     info.rho = q.rho;
+    if (WARM && c.warm) {  // the iterate for the next tick (before polishing, which starts its own system): valid only from a full window
+        WarmLayout wl;
+        wl.init(NH, NS, IdxT<L, FT>::nm);
+        const bool keep = K == NH && ok && warm_save(q, DEKF_SPAN(s.warm + (size_t)wl.len * b, wl.len), wl, cinv);
+        if (DEKF_LANE() == 0) s.warm_tag[b] = keep ? kstart + K - 1 : -1;
+    }
     // store_solution + update() tail: x_T = D x ; v_b = R (x_T[3:6] + gyro x p_imu_2_opti)
     cdptr rT = q.rec(K - 1);
     double xT[NS];
@@ -2245,6 +2370,14 @@ DEKF_FN SolveInfo solve_window_t(const DevCfg& c, const DevState& s, int b, int 
 #endif
     return info;
 }
+// the catalogue's entry (kernels.hip): solve_window_t with the polishing step and the warm start's code chosen per kernel
+template <bool POLISH, bool WARM>
+struct SolveEntry {
+    template <int L, bool FACTOR_LDS, bool PA_LDS, int NFIX = 0, int FT = 0, bool R3 = false>
+    DEKF_FN static SolveInfo run(const DevCfg& c, const DevState& s, int b, int kstart, int K, dptr lds, dptr gws) {
+        return solve_window_t<POLISH, L, FACTOR_LDS, PA_LDS, NFIX, FT, R3, WARM>(c, s, b, kstart, K, lds, gws);
+    }
+};
 // the kernels without the polishing step (osqp.polish false: parameters_go1.yaml:44 — the benchmark configuration)
 template <int L, bool FACTOR_LDS, bool PA_LDS, int NFIX = 0, int FT = 0, bool R3 = false>
 DEKF_FN SolveInfo solve_window(const DevCfg& c, const DevState& s, int b, int kstart, int K, dptr lds, dptr gws) {

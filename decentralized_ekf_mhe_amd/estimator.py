@@ -48,7 +48,8 @@ def _torch_runtime_first():
 
 
 class BatchedEstimator:
-    def __init__(self, params: DekfParams, batch: int, device: int = 0, stream=None):
+    def __init__(self, params: DekfParams, batch: int, device: int = 0, stream=None, warm_start: bool = False):
+        """warm_start: full-window solves start from the previous tick's shifted solution (dekf_set_warm_start; off by default)"""
         _torch_runtime_first()
         self.lib = capi.load()
         self.params = params.copy()
@@ -58,6 +59,12 @@ class BatchedEstimator:
         capi.check(self.lib.dekf_create(C.byref(self.params), batch, device, C.c_void_p(stream or 0), C.byref(h)))
         self.h = h
         self.T = 0
+        if warm_start:
+            try:
+                capi.check(self.lib.dekf_set_warm_start(self.h, 1))
+            except capi.DekfError:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "h", None):
@@ -156,6 +163,12 @@ class BatchedEstimator:
         out["polish_status"] = np.zeros(B, np.int32)
         capi.check(self.lib.dekf_get_polish_status(self.h, C.c_void_p(out["polish_status"].ctypes.data), capi.DEKF_HOST))
         return out
+
+    def warm_status(self):
+        """per instance: 1 if the last update's solve started from the shifted previous solution, 0 if it started cold"""
+        w = np.zeros(self.batch, np.int32)
+        capi.check(self.lib.dekf_get_warm_status(self.h, C.c_void_p(w.ctypes.data), capi.DEKF_HOST))
+        return w
 
     def ekf_cov(self):
         P = np.zeros((self.batch, 4, 4))

@@ -236,6 +236,29 @@ dekf_status dekf_get_polish_status(dekf_handle h, int* polish_status, dekf_mem w
 /* KF covariance C_KF_[B][dim_state][dim_state] (est_type 1). */
 dekf_status dekf_get_kf_cov(dekf_handle h, double* cov, dekf_mem where);
 
+/* ---- warm start (OSQP's warm_start setting; DecentralEst.cpp:204 asks for it) ------------------------------------
+ * Adding these two symbols does not change DEKF_ABI_VERSION: dekf_params is untouched, and a caller that never calls them gets
+ * exactly the cold-start solves (and bits) of before.
+ * dekf_set_warm_start(h, on), on = 0 or 1 (default 0): with 1, a full-window MHE solve starts from the previous tick's solution
+ * instead of x = z = y = 0 and rho = `rho`.  Allowed before dekf_initialize or right after dekf_reset (else DEKF_ERR_ORDER);
+ * DEKF_ERR_INVALID for a KF handle (est_type 1), a pipelined handle (solve_pipeline 1: solve T + 1 would need solve T's per-instance
+ * output while T's last workgroups still run) and any other `on`.  The first enable allocates the per-instance warm store
+ * ((n + m + 1) doubles, about 9 KB for Go1).
+ * Contract, per instance:
+ *  - window-fill ticks (T < N - 1) and the first full window start cold, bit-identical to warm start off;
+ *  - a full window starts warm only if the previous tick was a full window whose solve ended DEKF_SOLVE_OK or DEKF_SOLVE_MAX_ITER
+ *    with a finite iterate; otherwise cold.  dekf_reset invalidates every store.
+ *  - the previous iterate is SHIFTED by one window block (block k takes block k + 1; the entering x and leg slacks make this tick's
+ *    new Dyn and Meas rows hold exactly, the entering w, c and duals are 0), not reused index for index as osqp_warm_start would:
+ *    the window has slid one step, and index-for-index reuse would pair every block with its neighbour's value.  z = A x on the VO
+ *    rows; equality rows start on their bound.  x and y are kept unscaled and rescaled with this tick's Ruiz scaling.
+ *  - rho starts at the instance's final rho of the previous solve, clamped to [1e-6, 1e6].
+ *  - termination, adaptive rho, max_qp_iter, status codes and polishing are unchanged; dekf_get_solver_info reports the warm counts.
+ * dekf_get_warm_status: warm[B] (int) = 1 if the last update's solve started from the shifted previous iterate, 0 if cold.
+ * (dekf_solve_kernel_name of a warm handle names the full-window kernel's warm twin where it has one, e.g. k_mhe_solve_r3_4_n20_warm.) */
+dekf_status dekf_set_warm_start(dekf_handle h, int on);
+dekf_status dekf_get_warm_status(dekf_handle h, int* warm, dekf_mem where);
+
 /* status[B] values written by dekf_update */
 #define DEKF_SOLVE_NONE 0       /* no solve yet (T = 0) */
 #define DEKF_SOLVE_OK 1         /* OSQP_SOLVED */

@@ -6,6 +6,7 @@ absolute time of this build; read the shares.
 
     DEKF_LIB=decentralized_ekf_mhe_amd/csrc/libdekf_prof.so python tools/profile_sections.py [batch [ticks [go1|cassie|pogox|go1foot]]]
     DEKF_TIMELINE=1 DEKF_LIB=.../libdekf_tl.so python tools/profile_sections.py 4096 70   # -DDEKF_PROFILE -DDEKF_PROFILE_TL
+    DEKF_WARM=1 ...                                                                       # warm start on (dekf_set_warm_start)
 """
 import ctypes as C
 import json
@@ -47,7 +48,7 @@ def main():
         p.leg_odom_type = 1  # foot positions as states: 21-dim blocks, factor streamed from the HBM slab
     s = make_streams(p, B, K)
     sd = streams_to_device(s)
-    est = BatchedEstimator(p, B)
+    est = BatchedEstimator(p, B, warm_start=os.environ.get("DEKF_WARM", "0") == "1")
     for k in range(K):
         est.push_stream_step(sd, k)
         est.step(k)
