@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — estimator-steps/s of the EKF + 20-step-MHE hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Both forms work for N > 1: called plainly (no WORLD_SIZE in the environment), `main()` starts the N ranks itself as a
@@ -18,6 +18,11 @@ shards and exchange only the fused base-velocity estimates (one RCCL all-gather 
 shard is 4096 instances at N = 1 (configs[1]) and 8192 at N > 1, so that N = 8 is configs[3]
 "Go1, batch=65 536 sharded across 8xMI355X"; --batch overrides both.  Sensor logs are synthetic
 (decentralized_ekf_mhe_amd/streams.py) and resident in HBM before the timed region.
+
+A plain run does only what its line needs: set-up, window fill, warm-up, the K timed steps, --dump-outputs and the line.  What
+the line's figures do not need runs with --full only: the CPU baselines timed on this host (the oracle port and the product's own
+cores built for the host, a compile of its own) and the error of the final states against the oracle (`cpu_baseline`,
+`solver.max_rel_err_vs_oracle`, `solver.error_vs_oracle`).
 
 The rank choreography (`run_bench`) takes everything that touches a device through a `BenchEnv`, so that
 tests/test_bench_orchestration.py can run the very same code on two gloo ranks with a stand-in estimator; `main()`
@@ -517,7 +522,7 @@ def run_bench(args, env, rank, world):
         }
         if not env.real:
             line["stand_in"] = True  # tests only: no estimator ran, nothing in this line is a measurement
-        if not args.no_cpu_baseline and world == 1 and env.real:  # the CPU leg runs at N = 1 only (rank 0's host cores, same run)
+        if getattr(args, "full", False) and not args.no_cpu_baseline and world == 1 and env.real:  # the CPU leg runs at N = 1 only (rank 0's host cores, same run)
             cb = cpu_baseline(p, total, seed_first=0, gpu_x_final=out["x"])
             err = cb.pop("error_vs_oracle", None)
             line["cpu_baseline"] = cb
@@ -571,7 +576,9 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--batch", type=int, default=None, help="instances per GPU (default 4096 at --gpus 1, else 8192)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run what the line's own figures do not need: the CPU baselines on this "
+                    "host and the comparison of the final states with the oracle (cpu_baseline; at --gpus 1 only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed "
                     "(estimator outputs and solver report of rank 0's instances) to DIR/<name>.npy in float64")
     ap.add_argument("--no-allgather", action="store_true")

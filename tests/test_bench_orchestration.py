@@ -166,6 +166,30 @@ def test_workload_names_and_default_shards():
     assert "configs[3]" not in bench.workload_name(4096, 8, 20).replace("per-rank share of BASELINE.json configs[3]", "")
 
 
+def test_cpu_baseline_runs_with_full_only(monkeypatch):
+    """a plain run does only what its line needs; the CPU leg (oracle port, host build of the cores, error against the oracle)
+    runs with --full, after the timed steps, and lands in the line as before"""
+    calls = []
+
+    def fake_cpu_baseline(p, total, seed_first, gpu_x_final=None):
+        calls.append((total, seed_first, gpu_x_final.shape))
+        return {"value": 1.0, "error_vs_oracle": {"max_rel_err": 0.5}}
+    monkeypatch.setattr(bench, "cpu_baseline", fake_cpu_baseline)
+    assert bench.parse_args([]).full is False and bench.parse_args(["--full"]).full is True
+    lines = {}
+    for extra in ([], ["--full"], ["--full", "--no-cpu-baseline"]):
+        made = []
+        env = make_env(0, 0, 1, made=made)
+        env.real = True   # the CPU leg is only ever taken for the real estimator
+        args = bench.parse_args(["--steps", "3", "--warmup", "2", "--batch", "4"] + extra)
+        lines[" ".join(extra)] = bench.run_bench(args, env, 0, 1)
+        assert made[0].k == 64 + 3 - 1 and made[0].timed_steps == 3
+    assert calls == [(64 + 3, 0, (4, 9))]
+    assert "cpu_baseline" not in lines[""] and "max_rel_err_vs_oracle" not in lines[""]["solver"]
+    assert "cpu_baseline" not in lines["--full --no-cpu-baseline"]
+    assert lines["--full"]["cpu_baseline"] == {"value": 1.0} and lines["--full"]["solver"]["max_rel_err_vs_oracle"] == 0.5
+
+
 def test_dump_outputs_writes_what_the_last_timed_step_returned(tmp_path):
     """--dump-outputs DIR: the arrays the timed path hands its caller after its last step, one .npy each, in float64"""
     out = tmp_path / "dump"
