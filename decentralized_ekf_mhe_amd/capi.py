@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("DEKF_LIB", os.path.join(_HERE, "csrc", "libdekf.so"))
 DEKF_OK, DEKF_ERR_INVALID, DEKF_ERR_NO_DEVICE, DEKF_ERR_HIP, DEKF_ERR_ORDER, DEKF_ERR_COMM = range(6)
 DEKF_HOST, DEKF_DEVICE = 0, 1
 DEKF_SOLVE_NONE, DEKF_SOLVE_OK, DEKF_SOLVE_MAX_ITER, DEKF_SOLVE_NUMERIC = 0, 1, 2, -1
+DEKF_SOLVER_ADMM, DEKF_SOLVER_DIRECT = 0, 1
 DEKF_UNIQUE_ID_BYTES = 128
 DEKF_ABI_VERSION = 4  # include/dekf.h; the ctypes mirror of dekf_params (params.py) is laid out for exactly this version
 
@@ -47,6 +48,8 @@ PROTOTYPES = {
     "dekf_get_kf_cov": (C.c_int, [_vp, _vp, C.c_int]),
     "dekf_set_warm_start": (C.c_int, [_vp, C.c_int]),
     "dekf_get_warm_status": (C.c_int, [_vp, _vp, C.c_int]),
+    "dekf_set_solver": (C.c_int, [_vp, C.c_int]),
+    "dekf_get_mhe_cov": (C.c_int, [_vp, _vp, C.c_int]),
     "dekf_timing_enable": (C.c_int, [_vp, C.c_int]),
     "dekf_timing_read": (C.c_int, [_vp, _dp, _ip]),
     "dekf_launch_info": (C.c_int, [_vp, _ip, _ip, _dp]),

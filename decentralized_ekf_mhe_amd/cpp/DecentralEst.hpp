@@ -101,6 +101,9 @@ struct robot_params {
     // OSQP's warm_start (DecentralEst.cpp:204 sets it; the reference's solver is rebuilt every tick, so it never takes effect there):
     // full-window solves start from the previous tick's shifted solution (dekf_set_warm_start; MHE only)
     bool warmStart_ = false;
+    // new: the exact optimum of the window QP instead of the ADMM iterate, and Cov(x_T) in C_MHE_ after every update
+    // (dekf_set_solver(h, DEKF_SOLVER_DIRECT); MHE only, not with polish_ or warmStart_)
+    bool directSolve_ = false;
 };
 
 // ---- DecentralEst.hpp:65-94 ----------------------------------------------------------------
@@ -184,6 +187,9 @@ class DecentralizedEstimation {
         x_MHE_.resize(dim_state_);
         x_KF_.resize(dim_state_);
         C_KF_ = MatrixXd(dim_state_, dim_state_);
+        C_MHE_ = MatrixXd::Zero(dim_state_, dim_state_);
+        direct_ = params->directSolve_ && prm_.est_type == 0;
+        if (direct_) dekf_shim::check(dekf_set_solver(h_, DEKF_SOLVER_DIRECT));
         if (params->warmStart_ && prm_.est_type == 0) dekf_shim::check(dekf_set_warm_start(h_, 1));
         latch();
         dekf_shim::check(dekf_initialize(h_));
@@ -195,6 +201,11 @@ class DecentralizedEstimation {
         latch();
         dekf_shim::check(dekf_update(h_, T));
         fetch();
+        if (direct_) {
+            double C[(9 + 3 * DEKF_MAX_LEGS) * (9 + 3 * DEKF_MAX_LEGS)];
+            dekf_shim::check(dekf_get_mhe_cov(h_, C, DEKF_HOST));
+            for (int i = 0; i < dim_state_; ++i) for (int j = 0; j < dim_state_; ++j) C_MHE_(i, j) = C[dim_state_ * i + j];
+        }
     }
     // DecentralEst.cpp:1011-1015
     void reset() { if (h_) dekf_shim::check(dekf_reset(h_)); }
@@ -207,6 +218,7 @@ class DecentralizedEstimation {
     VectorXd x_KF_;
     MatrixXd C_KF_ = MatrixXd(9, 9);
     Vector3d v_KF_b_;
+    MatrixXd C_MHE_ = MatrixXd::Zero(9, 9);  // new: Cov(x_MHE_) of the last update of a direct handle (robot_params::directSolve_)
     int solver_status_ = DEKF_SOLVE_NONE, solver_iters_ = 0;  // new: the reference ignores OSQP's flag
     int dim_state_ = 9;                                       // 9 + 3 * leg_odom_type * num_legs
     // new: take raw Go1 joint states from robot_store (joint_states_position_/velocity_) instead of
@@ -218,6 +230,7 @@ class DecentralizedEstimation {
     std::shared_ptr<robot_params> params_ptr_;
     dekf_params prm_;
     dekf_handle h_ = nullptr;
+    bool direct_ = false;  // robot_params::directSolve_ on an MHE handle
 
     // what GetMeasurement reads from robot_store by pointer (DecentralEst.cpp:867-879)
     void latch() {

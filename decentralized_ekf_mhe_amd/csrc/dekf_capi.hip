@@ -13,6 +13,7 @@
 #include "host_common.h"
 #include "kf_core.h"
 #include "mhe_assemble_core.h"
+#include "mhe_direct_core.h"
 #include "mhe_solve_core.h"
 
 using namespace dekf;
@@ -29,6 +30,9 @@ __global__ void k_mhe_marginalize_early(DevCfg c, DevState s, int T);
     __global__ void NAME##_warm(DevCfg c, DevState s, int kstart, int K, int gws_len); \
     __global__ void NAME##_warm_pol(DevCfg c, DevState s, int kstart, int K, int gws_len);
 #include "solve_kernels.def"
+// the direct solve kernels (direct_kernels.def)
+#define DEKF_DIRECT_KERNEL(NAME, ...) __global__ void NAME(DevCfg c, DevState s, int kstart, int K, double* cov);
+#include "direct_kernels.def"
 __global__ void k_gap();
 __global__ void k_kf_initialize(DevCfg c, DevState s);
 __global__ void k_kf_update(DevCfg c, DevState s, int pushes);
@@ -48,7 +52,7 @@ struct RcclApi;  // rccl_dyn.h
 }  // namespace
 #include "rccl_dyn.h"
 
-namespace { struct SolveKernel; }
+namespace { struct SolveKernel; struct DirectKernel; }
 struct dekf_handle_s {
     dekf_params prm;
     DevCfg c;
@@ -69,6 +73,13 @@ struct dekf_handle_s {
     size_t lds_solve_full = 0;
     const char *solve_name = nullptr, *solve_name_full = nullptr;  // kernel symbols, for dekf_solve_kernel_name
     const SolveKernel* solve_entry_full = nullptr;  // the catalogue's row of solve_kernel_full (its warm twin: dekf_set_warm_start)
+    // dekf_set_solver: DEKF_SOLVER_ADMM (0) or DEKF_SOLVER_DIRECT (1).  A direct handle launches `direct` (one wavefront per instance,
+    // a grid of B) wherever an in-order ADMM handle launches its solve, and keeps Cov(x_T) of the last update in mhe_cov ([B][ns][ns])
+    int solver = DEKF_SOLVER_ADMM;
+    const DirectKernel* direct = nullptr;
+    double* mhe_cov = nullptr;
+    size_t lds_direct = 0;
+    bool mhe_cov_valid = false;  // an update has written mhe_cov since dekf_create / dekf_reset
     size_t lds_solve = 0, lds_asm = 0, lds_kf = 0;
     int ekf_count = 0, pushes = 0, next_T = 0;
     bool initialized = false;
@@ -152,6 +163,29 @@ const SolveKernel* solve_kernel(SolveRole role, int L, int N) {
     const SolveKernel* any = nullptr;
     for (const SolveKernel& k : solve_kernels) {
         if (k.role != role || k.legs != L) continue;
+        if (k.nfix == N) return &k;
+        if (k.nfix == 0) any = &k;
+    }
+    return any;
+}
+
+// The direct solve kernels as dekf_set_solver selects them: every row of direct_kernels.def
+typedef void (*DirectFn)(DevCfg, DevState, int, int, double*);
+struct DirectKernel {
+    int legs, ft, nfix;  // direct_solve_t's L and FT; the horizon the row is meant for (0: any)
+    DirectFn fn;
+    const char* name;
+};
+#define DEKF_DIRECT_KERNEL(NAME, L, FT, NFIX) {L, FT, NFIX, NAME, #NAME},
+const DirectKernel direct_kernels[] = {
+#include "direct_kernels.def"
+};
+
+// the direct kernel of the shape: the one meant for the horizon N if there is one, else the one for any horizon
+const DirectKernel* direct_kernel(int L, int ft, int N) {
+    const DirectKernel* any = nullptr;
+    for (const DirectKernel& k : direct_kernels) {
+        if (k.legs != L || k.ft != ft) continue;
         if (k.nfix == N) return &k;
         if (k.nfix == 0) any = &k;
     }
@@ -507,6 +541,7 @@ dekf_status dekf_reset(dekf_handle h) {
     h->pushes = 0;
     h->next_T = 0;
     h->initialized = false;
+    h->mhe_cov_valid = false;  // (the solver setting survives)
     return DEKF_OK;
 }
 
@@ -674,7 +709,9 @@ dekf_status dekf_update(dekf_handle h, int T) {
             { static const int gap = getenv("DEKF_DEBUG_GAP_KERNEL") ? atoi(getenv("DEKF_DEBUG_GAP_KERNEL")) : 0;
               for (int i = 0; i < gap; ++i) k_gap<<<1, 64, 0, ss>>>(); }
 #endif
-            if (h->solve_kernel_full && K == h->c.N)
+            if (h->solver == DEKF_SOLVER_DIRECT)
+                h->direct->fn<<<h->c.B, 64, h->lds_direct, ss>>>(h->c, sp, kstart, K, h->mhe_cov);
+            else if (h->solve_kernel_full && K == h->c.N)
                 h->solve_kernel_full<<<h->solve_grid_full, h->solve_threads_full, h->lds_solve_full, ss>>>(h->c, sp, kstart, K, h->gws_len);
             else
                 h->solve_kernel<<<h->solve_grid, DEKF_SOLVE_THREADS, h->lds_solve, ss>>>(h->c, sp, kstart, K, h->gws_len);
@@ -686,6 +723,7 @@ dekf_status dekf_update(dekf_handle h, int T) {
             h->snap_busy[snap_set] = true;
         }
         h->last_par = par;
+        h->mhe_cov_valid = h->solver == DEKF_SOLVER_DIRECT;
         if (h->early_stream) {
             // behind the assemble of this step (the arrival cost and the records as it left them), beside this step's solve
             HIPCHK(hipStreamWaitEvent(h->early_stream, h->ev_asm_done, 0));
@@ -775,6 +813,7 @@ dekf_status dekf_set_warm_start(dekf_handle h, int on) {
     if (h->c.est_type != 0) return fail(DEKF_ERR_INVALID, "warm start is an MHE setting: this is a KF handle (est_type 1)");
     if (h->pipelined) return fail(DEKF_ERR_INVALID, "warm start cannot be combined with solve_pipeline = 1");
     if (h->initialized) return fail(DEKF_ERR_ORDER, "dekf_set_warm_start is allowed before dekf_initialize or right after dekf_reset");
+    if (on && h->solver == DEKF_SOLVER_DIRECT) return fail(DEKF_ERR_INVALID, "warm start has no meaning for a direct solve (dekf_set_solver)");
     HIPCHK(hipSetDevice(h->device));
     if (on && !h->s.warm) {
         WarmLayout wl;
@@ -814,6 +853,43 @@ dekf_status dekf_get_warm_status(dekf_handle h, int* warm, dekf_mem where) {
     }
     dekf_status st;
     if ((st = fetch(h, warm, h->s.warm_used, n, where))) return st;
+    if (where == DEKF_HOST) HIPCHK(hipStreamSynchronize(h->stream));
+    return DEKF_OK;
+}
+
+dekf_status dekf_set_solver(dekf_handle h, int solver) {
+    if (!h) return fail(DEKF_ERR_INVALID, "null handle");
+    if (solver != DEKF_SOLVER_ADMM && solver != DEKF_SOLVER_DIRECT)
+        return fail(DEKF_ERR_INVALID, "dekf_set_solver: solver must be DEKF_SOLVER_ADMM (0) or DEKF_SOLVER_DIRECT (1)");
+    if (h->c.est_type != 0) return fail(DEKF_ERR_INVALID, "the solver is an MHE setting: this is a KF handle (est_type 1)");
+    if (h->pipelined) return fail(DEKF_ERR_INVALID, "dekf_set_solver cannot be combined with solve_pipeline = 1");
+    if (h->initialized) return fail(DEKF_ERR_ORDER, "dekf_set_solver is allowed before dekf_initialize or right after dekf_reset");
+    if (solver == DEKF_SOLVER_DIRECT) {
+        if (h->c.polish) return fail(DEKF_ERR_INVALID, "the direct solve cannot be combined with osqp.polish = 1");
+        if (h->c.warm) return fail(DEKF_ERR_INVALID, "the direct solve cannot be combined with warm start (dekf_set_warm_start)");
+        const DirectKernel* k = direct_kernel(h->c.L, h->c.ft, h->c.N);
+        if (!k) return fail(DEKF_ERR_INVALID, "no direct solve kernel for this shape");
+        HIPCHK(hipSetDevice(h->device));
+        if (!h->mhe_cov) {
+            double* cv = nullptr;
+            HIPCHK(hipMalloc(&cv, (size_t)h->c.B * h->c.ns * h->c.ns * sizeof(double)));
+            h->blocks.push_back(cv);
+            h->mhe_cov = cv;
+        }
+        h->direct = k;
+        h->lds_direct = (size_t)DirectScratch::len(h->c.ns) * sizeof(double);
+    }
+    h->solver = solver;
+    h->mhe_cov_valid = false;
+    return DEKF_OK;
+}
+
+dekf_status dekf_get_mhe_cov(dekf_handle h, double* cov, dekf_mem where) {
+    if (!h || !cov) return fail(DEKF_ERR_INVALID, "null argument");
+    if (h->solver != DEKF_SOLVER_DIRECT) return fail(DEKF_ERR_INVALID, "dekf_get_mhe_cov needs a direct handle (dekf_set_solver(h, DEKF_SOLVER_DIRECT))");
+    if (!h->mhe_cov_valid) return fail(DEKF_ERR_ORDER, "dekf_get_mhe_cov before the first update (since dekf_create or dekf_reset)");
+    dekf_status st = fetch(h, cov, h->mhe_cov, (size_t)h->c.ns * h->c.ns * h->c.B * 8, where);
+    if (st) return st;
     if (where == DEKF_HOST) HIPCHK(hipStreamSynchronize(h->stream));
     return DEKF_OK;
 }
@@ -869,7 +945,7 @@ dekf_status dekf_launch_info(dekf_handle h, int* solve_workgroups, int* compute_
     if (!h) return fail(DEKF_ERR_INVALID, "null handle");
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, h->device));
-    if (solve_workgroups) *solve_workgroups = h->solve_kernel_full ? h->solve_grid_full : h->solve_grid;
+    if (solve_workgroups) *solve_workgroups = h->solver == DEKF_SOLVER_DIRECT ? h->c.B : (h->solve_kernel_full ? h->solve_grid_full : h->solve_grid);
     if (compute_units) *compute_units = prop.multiProcessorCount;
     if (clock_hz) *clock_hz = (double)prop.clockRate * 1e3;
     return DEKF_OK;
@@ -877,6 +953,7 @@ dekf_status dekf_launch_info(dekf_handle h, int* solve_workgroups, int* compute_
 
 const char* dekf_solve_kernel_name(dekf_handle h, int full_window) {
     if (!h || h->c.est_type != 0) return nullptr;
+    if (h->solver == DEKF_SOLVER_DIRECT) return h->direct->name;
     return (full_window && h->solve_kernel_full) ? h->solve_name_full : h->solve_name;
 }
 

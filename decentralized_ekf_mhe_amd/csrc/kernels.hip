@@ -6,6 +6,7 @@
 //                     workgroup owns one scratch slab in HBM, so a slab is only ever touched
 //                     from one XCD (its L2 is the only one that caches it)
 //                     (mhe_solve_core.h, mhe_admm_core.h)
+//   k_mhe_solve_direct_*  the direct solve (dekf_set_solver), one wavefront per instance (mhe_direct_core.h)
 //   k_kf_*            KF alternative                      (kf_core.h)
 //   k_latch_vo        masked VO latch (robotSub::vo_callback for a batch)
 //   k_latch4          device-to-device sensor latch of one push (IMU or leg arrays) in one launch
@@ -16,6 +17,7 @@
 #include "go1_kin.h"
 #include "kf_core.h"
 #include "mhe_assemble_core.h"
+#include "mhe_direct_core.h"
 #include "mhe_solve_core.h"
 
 using namespace dekf;
@@ -191,6 +193,20 @@ __global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_marginalize_early(De
 #define DEKF_SOLVE_KERNEL_OFF(NAME, ...) DEKF_SOLVE_STUB_(NAME) DEKF_SOLVE_STUB_(NAME##_pol) DEKF_SOLVE_STUB_(NAME##_warm) DEKF_SOLVE_STUB_(NAME##_warm_pol)
 #endif
 #include "solve_kernels.def"
+
+// The direct solve kernels (direct_kernels.def): one wavefront per instance, a grid of B; every instance does the same work, so the
+// instance queue of the ADMM kernels would gain nothing.  cov: Cov(x_T) per instance, [B][ns][ns].
+#define DEKF_DIRECT_KERNEL(NAME, L, FT, NFIX)                                                                                 \
+    __global__ void __launch_bounds__(64) NAME(DevCfg c, DevState s, int kstart, int K, double* cov) {                         \
+        extern __shared__ double lds[];                                                                                      \
+        direct_solve_t<L, FT>(c, s, blockIdx.x, kstart, K, lds, cov);                                                         \
+    }
+#ifdef DEKF_KSET_ONLY
+#define DEKF_DIRECT_KERNEL_OFF(...)
+#else
+#define DEKF_DIRECT_KERNEL_OFF(NAME, ...) __global__ void NAME(DevCfg, DevState, int, int, double*) {}
+#endif
+#include "direct_kernels.def"
 
 #if DEKF_MISC_KERNELS
 __global__ void k_gap() {}

@@ -48,8 +48,12 @@ def _torch_runtime_first():
 
 
 class BatchedEstimator:
-    def __init__(self, params: DekfParams, batch: int, device: int = 0, stream=None, warm_start: bool = False):
-        """warm_start: full-window solves start from the previous tick's shifted solution (dekf_set_warm_start; off by default)"""
+    def __init__(self, params: DekfParams, batch: int, device: int = 0, stream=None, warm_start: bool = False, solver: str = "admm"):
+        """warm_start: full-window solves start from the previous tick's shifted solution (dekf_set_warm_start; off by default).
+        solver: "admm" (default, the reference's OSQP-style ADMM) or "direct" (the exact optimum of the window QP and its covariance,
+        dekf_set_solver; see mhe_cov)"""
+        if solver not in ("admm", "direct"):
+            raise ValueError(f"solver must be 'admm' or 'direct', not {solver!r}")
         _torch_runtime_first()
         self.lib = capi.load()
         self.params = params.copy()
@@ -59,12 +63,14 @@ class BatchedEstimator:
         capi.check(self.lib.dekf_create(C.byref(self.params), batch, device, C.c_void_p(stream or 0), C.byref(h)))
         self.h = h
         self.T = 0
-        if warm_start:
-            try:
+        try:
+            if solver == "direct":
+                capi.check(self.lib.dekf_set_solver(self.h, capi.DEKF_SOLVER_DIRECT))
+            if warm_start:
                 capi.check(self.lib.dekf_set_warm_start(self.h, 1))
-            except capi.DekfError:
-                self.close()
-                raise
+        except capi.DekfError:
+            self.close()
+            raise
 
     def close(self):
         if getattr(self, "h", None):
@@ -174,6 +180,13 @@ class BatchedEstimator:
         P = np.zeros((self.batch, 4, 4))
         capi.check(self.lib.dekf_get_ekf_cov(self.h, C.c_void_p(P.ctypes.data), capi.DEKF_HOST))
         return P
+
+    def mhe_cov(self):
+        """Cov(x_T) [B, ns, ns] of the last update of a direct handle (dekf_get_mhe_cov)"""
+        ns = self.params.dim_state
+        Cm = np.zeros((self.batch, ns, ns))
+        capi.check(self.lib.dekf_get_mhe_cov(self.h, C.c_void_p(Cm.ctypes.data), capi.DEKF_HOST))
+        return Cm
 
     def kf_cov(self):
         ns = self.params.dim_state

@@ -259,6 +259,33 @@ dekf_status dekf_get_kf_cov(dekf_handle h, double* cov, dekf_mem where);
 dekf_status dekf_set_warm_start(dekf_handle h, int on);
 dekf_status dekf_get_warm_status(dekf_handle h, int* warm, dekf_mem where);
 
+/* ---- direct solve (opt-in): the exact optimum of the window QP and the covariance of its newest state ---------------
+ * Adding these two symbols does not change DEKF_ABI_VERSION: dekf_params is untouched, and a caller that never calls them gets
+ * exactly the ADMM solves (and bits) of before.
+ * dekf_set_solver(h, solver), solver = DEKF_SOLVER_ADMM (default: the reference's OSQP-style ADMM) or DEKF_SOLVER_DIRECT.  Allowed
+ * before dekf_initialize or right after dekf_reset (else DEKF_ERR_ORDER); the setting survives dekf_reset.  DEKF_ERR_INVALID for any
+ * other value, a KF handle (est_type 1) and a pipelined handle (solve_pipeline 1), and DEKF_ERR_INVALID for DEKF_SOLVER_DIRECT on a
+ * handle with osqp.polish = 1 or with warm start on; dekf_set_warm_start(h, 1) on a direct handle is DEKF_ERR_INVALID too.  Polishing
+ * and warm start act on an ADMM iterate, which a direct solve does not have.  The first DEKF_SOLVER_DIRECT allocates the covariance
+ * store (B dim_state^2 doubles).
+ * Contract of a direct handle, per instance and update (window-fill and full windows alike):
+ *  - "exact": x_mhe is the newest state of the minimiser of the window QP with every row whose bounds are finite held as an equality
+ *    (every Meas and Dyn row; a VO row once vision has written its bound) and every +-1e30 row free — one forward block elimination
+ *    over the window (the Kalman filter on the window when no VO row is an equality), with the arrival cost of the ADMM path.  It
+ *    differs from an ADMM handle's x_mhe by the ADMM iterate's own distance from that optimum (within OSQP's eps, not bit-equal);
+ *  - v_b as on an ADMM handle, from that x_mhe;
+ *  - status DEKF_SOLVE_OK, or DEKF_SOLVE_NUMERIC for a non-positive or non-finite pivot or a non-finite result; iters = rho_updates
+ *    = 0, polish_status = 0, and pri_res = dua_res = NaN (no ADMM iterate exists);
+ *  - dekf_solve_kernel_name names the direct kernel (k_mhe_solve_direct_*) for both window kinds, dekf_launch_info reports B
+ *    workgroups (one wavefront each), timing class 2 brackets the direct launch.
+ * dekf_get_mhe_cov: cov[B][dim_state][dim_state] (row-major) = Cov(x_T) = [J^-1]_TT of the last update, J the information matrix of
+ * the window's states.  DEKF_ERR_INVALID on an ADMM or KF handle, DEKF_ERR_ORDER before the first update and after dekf_reset until
+ * the next update. */
+#define DEKF_SOLVER_ADMM 0   /* default: OSQP-style ADMM, the reference's solver */
+#define DEKF_SOLVER_DIRECT 1 /* exact optimum of the window QP by one forward block elimination */
+dekf_status dekf_set_solver(dekf_handle h, int solver);
+dekf_status dekf_get_mhe_cov(dekf_handle h, double* cov, dekf_mem where); /* cov[B][ns][ns], row-major */
+
 /* status[B] values written by dekf_update */
 #define DEKF_SOLVE_NONE 0       /* no solve yet (T = 0) */
 #define DEKF_SOLVE_OK 1         /* OSQP_SOLVED */

@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""Cold ADMM, warm ADMM (dekf_set_warm_start) and the direct solve (dekf_set_solver(h, DEKF_SOLVER_DIRECT)) on the four BASELINE
+shapes: Go1 B=4096, Cassie B=4096, PogoX B=1024 (N = 100) and Go1 with foot-position states (leg_odom_type 1) B=4096.  One JSON line
+per shape, the three modes side by side, each with
+  steps_per_s   over `steps` timed steps after the window has filled (device-resident logs, the loop of tools/warm_start_bench.py)
+  solve_ms      average launch time of the MHE solve (timing class 2, HIP events), in a second pass over the same steps
+  assemble_ms   average launch time of the term construction (timing class 1: k_mhe_assemble), same pass
+  kernel        the full-window solve kernel
+and appends them to profiles/r08_direct_bench.jsonl (--out).  Timing class 1 and 2 events are only on in the second pass, so
+steps_per_s is measured without them.
+    python tools/direct_bench.py [shape ...] [--steps 200] [--out profiles/r08_direct_bench.jsonl]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from decentralized_ekf_mhe_amd import cassie_params, go1_params, pogox_params  # noqa: E402
+from decentralized_ekf_mhe_amd.estimator import BatchedEstimator, streams_to_device  # noqa: E402
+from decentralized_ekf_mhe_amd.streams import make_streams  # noqa: E402
+
+SHAPES = {
+    "go1": (go1_params, 4096, {}),
+    "cassie": (cassie_params, 4096, {}),
+    "pogox": (pogox_params, 1024, {}),
+    "go1_foot": (go1_params, 4096, {"leg_odom_type": 1}),
+}
+MODES = {"cold": dict(), "warm": dict(warm_start=True), "direct": dict(solver="direct")}
+
+
+def one(p, B, sd, W, steps, mode):
+    est = BatchedEstimator(p, B, **MODES[mode])
+    for k in range(W):
+        est.push_stream_step(sd, k)
+        est.step(k)
+    est.sync()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for k in range(W, W + steps):
+        est.push_stream_step(sd, k)
+        est.step(k)
+    est.sync()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    # the same steps once more with events around the assemble and the solve launches (a handle's steps are not repeatable, so a second
+    # handle replays the log: same inputs, same kernels)
+    est2 = BatchedEstimator(p, B, **MODES[mode])
+    for k in range(W):
+        est2.push_stream_step(sd, k)
+        est2.step(k)
+    est2.sync()
+    est2.timing_enable(1)
+    for k in range(W, W + steps):
+        est2.push_stream_step(sd, k)
+        est2.step(k)
+    tim = est2.timing_read()
+    solved = float((est2.get()["status"] == 1).mean())
+    kernel = est.solve_kernel_name(True)
+    est.close()
+    est2.close()
+    return {"steps_per_s": B * steps / dt, "solve_ms": tim["solve"][0] / max(tim["solve"][1], 1),
+            "assemble_ms": tim["assemble"][0] / max(tim["assemble"][1], 1), "ekf_ms": tim["ekf"][0] / max(tim["ekf"][1], 1),
+            "solved_fraction": solved, "kernel": kernel}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("shapes", nargs="*", default=list(SHAPES))
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--modes", default="cold,warm,direct")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08_direct_bench.jsonl"))
+    a = ap.parse_args()
+    for name in a.shapes:
+        maker, B, kw = SHAPES[name]
+        p = maker()
+        p.ekf_rate = p.rate
+        for k, v in kw.items():
+            setattr(p, k, v)
+        W = max(p.N + 10, 64)  # (as tools/bench_shapes.py: past the window fill and the first vision intervals)
+        sd = streams_to_device(make_streams(p, B, W + a.steps))
+        line = {"shape": name, "batch": B, "N": int(p.N), "steps": a.steps}
+        for mode in a.modes.split(","):
+            line[mode] = one(p, B, sd, W, a.steps, mode)
+        if "direct" in line:
+            line.update({f"direct_over_{m}": line["direct"]["steps_per_s"] / line[m]["steps_per_s"] for m in ("cold", "warm") if m in line})
+        print(json.dumps(line), flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(json.dumps(line) + "\n")
+        del sd
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
