@@ -104,6 +104,9 @@ struct robot_params {
     // new: the exact optimum of the window QP instead of the ADMM iterate, and Cov(x_T) in C_MHE_ after every update
     // (dekf_set_solver(h, DEKF_SOLVER_DIRECT); MHE only, not with polish_ or warmStart_)
     bool directSolve_ = false;
+    // new: the window smoother of the direct solve: every state of the window and its covariance in x_window_ / C_window_ after
+    // every update (dekf_set_smoother; needs directSolve_)
+    bool smoothWindow_ = false;
 };
 
 // ---- DecentralEst.hpp:65-94 ----------------------------------------------------------------
@@ -190,6 +193,11 @@ class DecentralizedEstimation {
         C_MHE_ = MatrixXd::Zero(dim_state_, dim_state_);
         direct_ = params->directSolve_ && prm_.est_type == 0;
         if (direct_) dekf_shim::check(dekf_set_solver(h_, DEKF_SOLVER_DIRECT));
+        smooth_ = params->smoothWindow_ && prm_.est_type == 0;
+        if (smooth_) dekf_shim::check(dekf_set_smoother(h_, 1));
+        window_steps_ = 0;
+        x_window_.clear();
+        C_window_.clear();
         if (params->warmStart_ && prm_.est_type == 0) dekf_shim::check(dekf_set_warm_start(h_, 1));
         latch();
         dekf_shim::check(dekf_initialize(h_));
@@ -206,6 +214,19 @@ class DecentralizedEstimation {
             dekf_shim::check(dekf_get_mhe_cov(h_, C, DEKF_HOST));
             for (int i = 0; i < dim_state_; ++i) for (int j = 0; j < dim_state_; ++j) C_MHE_(i, j) = C[dim_state_ * i + j];
         }
+        if (smooth_) {
+            const size_t ns = (size_t)dim_state_, N = (size_t)prm_.N;
+            win_x_.resize(N * ns);
+            win_C_.resize(N * ns * ns);
+            dekf_shim::check(dekf_get_window(h_, &window_steps_, win_x_.data(), win_C_.data(), DEKF_HOST));
+            x_window_.assign((size_t)window_steps_, VectorXd(dim_state_));
+            C_window_.assign((size_t)window_steps_, MatrixXd(dim_state_, dim_state_));
+            for (size_t k = 0; k < (size_t)window_steps_; ++k)
+                for (size_t i = 0; i < ns; ++i) {
+                    x_window_[k]((int)i) = win_x_[ns * k + i];
+                    for (size_t j = 0; j < ns; ++j) C_window_[k]((int)i, (int)j) = win_C_[ns * ns * k + ns * i + j];
+                }
+        }
     }
     // DecentralEst.cpp:1011-1015
     void reset() { if (h_) dekf_shim::check(dekf_reset(h_)); }
@@ -219,6 +240,11 @@ class DecentralizedEstimation {
     MatrixXd C_KF_ = MatrixXd(9, 9);
     Vector3d v_KF_b_;
     MatrixXd C_MHE_ = MatrixXd::Zero(9, 9);  // new: Cov(x_MHE_) of the last update of a direct handle (robot_params::directSolve_)
+    // new: the window of the last update of a smoothing handle (robot_params::smoothWindow_): x_k and Cov(x_k) of its window_steps_
+    // steps, [0] the oldest, [window_steps_ - 1] = x_MHE_ / C_MHE_
+    int window_steps_ = 0;
+    std::vector<VectorXd> x_window_;
+    std::vector<MatrixXd> C_window_;
     int solver_status_ = DEKF_SOLVE_NONE, solver_iters_ = 0;  // new: the reference ignores OSQP's flag
     int dim_state_ = 9;                                       // 9 + 3 * leg_odom_type * num_legs
     // new: take raw Go1 joint states from robot_store (joint_states_position_/velocity_) instead of
@@ -231,6 +257,8 @@ class DecentralizedEstimation {
     dekf_params prm_;
     dekf_handle h_ = nullptr;
     bool direct_ = false;  // robot_params::directSolve_ on an MHE handle
+    bool smooth_ = false;  // robot_params::smoothWindow_ on an MHE handle
+    std::vector<double> win_x_, win_C_;
 
     // what GetMeasurement reads from robot_store by pointer (DecentralEst.cpp:867-879)
     void latch() {

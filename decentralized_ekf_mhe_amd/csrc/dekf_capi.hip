@@ -31,7 +31,9 @@ __global__ void k_mhe_marginalize_early(DevCfg c, DevState s, int T);
     __global__ void NAME##_warm_pol(DevCfg c, DevState s, int kstart, int K, int gws_len);
 #include "solve_kernels.def"
 // the direct solve kernels (direct_kernels.def)
-#define DEKF_DIRECT_KERNEL(NAME, ...) __global__ void NAME(DevCfg c, DevState s, int kstart, int K, double* cov);
+#define DEKF_DIRECT_KERNEL(NAME, ...)                                               \
+    __global__ void NAME(DevCfg c, DevState s, int kstart, int K, double* cov);   \
+    __global__ void NAME##_smooth(DevCfg c, DevState s, int kstart, int K, double* cov, DirectWindow win);
 #include "direct_kernels.def"
 __global__ void k_gap();
 __global__ void k_kf_initialize(DevCfg c, DevState s);
@@ -80,6 +82,12 @@ struct dekf_handle_s {
     double* mhe_cov = nullptr;
     size_t lds_direct = 0;
     bool mhe_cov_valid = false;  // an update has written mhe_cov since dekf_create / dekf_reset
+    // dekf_set_smoother: a smoothing direct handle launches the direct kernel's twin (direct->fn_smooth), which also leaves x_k and
+    // Cov(x_k) of every window step in win.x / win.cov (mhe_direct_core.h: DirectWindow); win_steps: K of the last update, 0 before
+    // the first one since dekf_create / dekf_reset
+    bool smoother = false;
+    DirectWindow win;
+    int win_steps = 0;
     size_t lds_solve = 0, lds_asm = 0, lds_kf = 0;
     int ekf_count = 0, pushes = 0, next_T = 0;
     bool initialized = false;
@@ -171,12 +179,15 @@ const SolveKernel* solve_kernel(SolveRole role, int L, int N) {
 
 // The direct solve kernels as dekf_set_solver selects them: every row of direct_kernels.def
 typedef void (*DirectFn)(DevCfg, DevState, int, int, double*);
+typedef void (*DirectSmoothFn)(DevCfg, DevState, int, int, double*, DirectWindow);
 struct DirectKernel {
     int legs, ft, nfix;  // direct_solve_t's L and FT; the horizon the row is meant for (0: any)
     DirectFn fn;
     const char* name;
+    DirectSmoothFn fn_smooth;  // the smoothing twin (dekf_set_smoother)
+    const char* name_smooth;
 };
-#define DEKF_DIRECT_KERNEL(NAME, L, FT, NFIX) {L, FT, NFIX, NAME, #NAME},
+#define DEKF_DIRECT_KERNEL(NAME, L, FT, NFIX) {L, FT, NFIX, NAME, #NAME, NAME##_smooth, #NAME "_smooth"},
 const DirectKernel direct_kernels[] = {
 #include "direct_kernels.def"
 };
@@ -541,7 +552,8 @@ dekf_status dekf_reset(dekf_handle h) {
     h->pushes = 0;
     h->next_T = 0;
     h->initialized = false;
-    h->mhe_cov_valid = false;  // (the solver setting survives)
+    h->mhe_cov_valid = false;  // (the solver and smoother settings survive)
+    h->win_steps = 0;
     return DEKF_OK;
 }
 
@@ -709,7 +721,9 @@ dekf_status dekf_update(dekf_handle h, int T) {
             { static const int gap = getenv("DEKF_DEBUG_GAP_KERNEL") ? atoi(getenv("DEKF_DEBUG_GAP_KERNEL")) : 0;
               for (int i = 0; i < gap; ++i) k_gap<<<1, 64, 0, ss>>>(); }
 #endif
-            if (h->solver == DEKF_SOLVER_DIRECT)
+            if (h->solver == DEKF_SOLVER_DIRECT && h->smoother)
+                h->direct->fn_smooth<<<h->c.B, 64, h->lds_direct, ss>>>(h->c, sp, kstart, K, h->mhe_cov, h->win);
+            else if (h->solver == DEKF_SOLVER_DIRECT)
                 h->direct->fn<<<h->c.B, 64, h->lds_direct, ss>>>(h->c, sp, kstart, K, h->mhe_cov);
             else if (h->solve_kernel_full && K == h->c.N)
                 h->solve_kernel_full<<<h->solve_grid_full, h->solve_threads_full, h->lds_solve_full, ss>>>(h->c, sp, kstart, K, h->gws_len);
@@ -724,6 +738,7 @@ dekf_status dekf_update(dekf_handle h, int T) {
         }
         h->last_par = par;
         h->mhe_cov_valid = h->solver == DEKF_SOLVER_DIRECT;
+        h->win_steps = h->smoother ? T - kstart + 1 : 0;
         if (h->early_stream) {
             // behind the assemble of this step (the arrival cost and the records as it left them), beside this step's solve
             HIPCHK(hipStreamWaitEvent(h->early_stream, h->ev_asm_done, 0));
@@ -881,6 +896,49 @@ dekf_status dekf_set_solver(dekf_handle h, int solver) {
     }
     h->solver = solver;
     h->mhe_cov_valid = false;
+    if (solver == DEKF_SOLVER_ADMM) h->smoother = false;  // the smoother is the direct solve's: switched off with it
+    h->win_steps = 0;
+    return DEKF_OK;
+}
+
+dekf_status dekf_set_smoother(dekf_handle h, int on) {
+    if (!h) return fail(DEKF_ERR_INVALID, "null handle");
+    if (on != 0 && on != 1) return fail(DEKF_ERR_INVALID, "dekf_set_smoother: on must be 0 or 1");
+    if (on && h->solver != DEKF_SOLVER_DIRECT) return fail(DEKF_ERR_INVALID, "the window smoother needs a direct handle (dekf_set_solver(h, DEKF_SOLVER_DIRECT))");
+    if (h->initialized) return fail(DEKF_ERR_ORDER, "dekf_set_smoother is allowed before dekf_initialize or right after dekf_reset");
+    if (on && !h->win.x) {
+        HIPCHK(hipSetDevice(h->device));
+        const size_t B = (size_t)h->c.B, N = (size_t)h->c.N, ns = (size_t)h->c.ns;
+        double* st = nullptr;  // x | cov | t1 in one block
+        HIPCHK(hipMalloc(&st, B * (N * ns + (2 * N - 1) * ns * ns) * sizeof(double)));
+        h->blocks.push_back(st);
+        h->win.x = st;
+        h->win.cov = st + B * N * ns;
+        h->win.t1 = h->win.cov + B * N * ns * ns;
+    }
+    h->smoother = on != 0;
+    h->win_steps = 0;
+    return DEKF_OK;
+}
+
+dekf_status dekf_get_window(dekf_handle h, int* steps, double* x_win, double* cov_win, dekf_mem where) {
+    if (!h) return fail(DEKF_ERR_INVALID, "null handle");
+    if (!h->smoother) return fail(DEKF_ERR_INVALID, "dekf_get_window needs a smoothing handle (dekf_set_smoother(h, 1))");
+    if (!h->win_steps) return fail(DEKF_ERR_ORDER, "dekf_get_window before the first update (since dekf_create or dekf_reset)");
+    const size_t N = (size_t)h->c.N, ns = (size_t)h->c.ns, K = (size_t)h->win_steps;
+    if (steps) *steps = h->win_steps;
+    // the K written entries of every instance: [B][N][...] with a pitch of N entries on both sides
+    const hipMemcpyKind kind = where == DEKF_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    const size_t B = (size_t)h->c.B;
+    if (K == N) {  // full windows: one contiguous copy each
+        dekf_status st;
+        if ((st = fetch(h, x_win, h->win.x, B * N * ns * 8, where))) return st;
+        if ((st = fetch(h, cov_win, h->win.cov, B * N * ns * ns * 8, where))) return st;
+    } else {
+        if (x_win) HIPCHK(hipMemcpy2DAsync(x_win, N * ns * 8, h->win.x, N * ns * 8, K * ns * 8, B, kind, h->stream));
+        if (cov_win) HIPCHK(hipMemcpy2DAsync(cov_win, N * ns * ns * 8, h->win.cov, N * ns * ns * 8, K * ns * ns * 8, B, kind, h->stream));
+    }
+    if (where == DEKF_HOST && (x_win || cov_win)) HIPCHK(hipStreamSynchronize(h->stream));
     return DEKF_OK;
 }
 
@@ -953,7 +1011,7 @@ dekf_status dekf_launch_info(dekf_handle h, int* solve_workgroups, int* compute_
 
 const char* dekf_solve_kernel_name(dekf_handle h, int full_window) {
     if (!h || h->c.est_type != 0) return nullptr;
-    if (h->solver == DEKF_SOLVER_DIRECT) return h->direct->name;
+    if (h->solver == DEKF_SOLVER_DIRECT) return h->smoother ? h->direct->name_smooth : h->direct->name;
     return (full_window && h->solve_kernel_full) ? h->solve_name_full : h->solve_name;
 }
 

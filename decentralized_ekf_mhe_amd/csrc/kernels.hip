@@ -196,15 +196,23 @@ __global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_marginalize_early(De
 
 // The direct solve kernels (direct_kernels.def): one wavefront per instance, a grid of B; every instance does the same work, so the
 // instance queue of the ADMM kernels would gain nothing.  cov: Cov(x_T) per instance, [B][ns][ns].
+// Every row also defines its smoothing twin NAME_smooth (dekf_set_smoother): direct_solve_t's SMOOTH instantiation, the backward pass
+// in the same launch; win: the window stores (mhe_direct_core.h: DirectWindow).  NAME itself is the instantiation it was.
 #define DEKF_DIRECT_KERNEL(NAME, L, FT, NFIX)                                                                                 \
     __global__ void __launch_bounds__(64) NAME(DevCfg c, DevState s, int kstart, int K, double* cov) {                         \
         extern __shared__ double lds[];                                                                                      \
         direct_solve_t<L, FT>(c, s, blockIdx.x, kstart, K, lds, cov);                                                         \
+    }                                                                                                                        \
+    __global__ void __launch_bounds__(64) NAME##_smooth(DevCfg c, DevState s, int kstart, int K, double* cov, DirectWindow win) { \
+        extern __shared__ double lds[];                                                                                      \
+        direct_solve_t<L, FT, true>(c, s, blockIdx.x, kstart, K, lds, cov, win);                                              \
     }
 #ifdef DEKF_KSET_ONLY
 #define DEKF_DIRECT_KERNEL_OFF(...)
 #else
-#define DEKF_DIRECT_KERNEL_OFF(NAME, ...) __global__ void NAME(DevCfg, DevState, int, int, double*) {}
+#define DEKF_DIRECT_KERNEL_OFF(NAME, ...)                               \
+    __global__ void NAME(DevCfg, DevState, int, int, double*) {}        \
+    __global__ void NAME##_smooth(DevCfg, DevState, int, int, double*, DirectWindow) {}
 #endif
 #include "direct_kernels.def"
 

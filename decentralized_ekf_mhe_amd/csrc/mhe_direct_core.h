@@ -15,6 +15,16 @@
 // and Cov(x_T) = Lambda_{K-1}^-1 = [J^-1]_TT.  No back-substitution: x_mhe is x_T alone.  Without VO rows this is the Kalman filter
 // on the window, in information form.
 //
+// The window smoother (SMOOTH, dekf_set_smoother): eliminating x_k left the conditional x_k | x_{k+1} ~ N(Li_k (r_k + G_k'x_{k+1}), Li_k)
+// with Li_k = Lambda_k^-1, so with u_k = Li_k r_k and T1_k = G_k Li_k (the smoother gain is T1_k') the backward (Rauch-Tung-Striebel)
+// recursion gives every state of the window and its covariance:
+//     x_{K-1} = u_{K-1}                 P_{K-1} = Li_{K-1}                       (what the forward pass ends with)
+//     x_k = u_k + T1_k' x_{k+1}         P_k = Li_k + T1_k' P_{k+1} T1_k          k = K-2 .. 0
+// G_k carries the E'Q_c E term of an equality VO row, so nothing about VO is special here.  The forward pass keeps u_k, Li_k and T1_k in
+// three per-instance stores (DirectWindow, indexed by window position k, not ring slot); the backward pass, in the same kernel, turns
+// the first two into x_k and P_k in place, x_{k+1} and P_{k+1} staying in LDS.  The forward pass and everything it writes are the same
+// instructions on the same values with and without SMOOTH.
+//
 // Inputs are exactly what solve_window_t reads: the window records at ring slot (kstart + k) % wcap (Meas from Rec::BM / qm, Dyn
 // from Rec::AS / QD and the bias gains, VO gains from Rec::QC) and, from the solve's input snapshot (DevState::snap), the arrival
 // cost and the VO flag / bound of every slot.  Qd | Qc of the newest record are never read (k_mhe_marginalize_early of the next step
@@ -31,6 +41,14 @@ namespace dekf {
 // LDS of one instance (doubles): M | h | Lambda | r | G | Qb | T1 | Lambda^-1 | d | scratch of the lane-sequential inverse
 struct DirectScratch {
     DEKF_HD static int len(int ns) { return 5 * ns * ns + 6 * ns + 8; }
+};
+
+// The window smoother's stores (dekf_set_smoother), [B][...] each: x [N][ns] and cov [N][ns^2] are the outputs (window position k = 0
+// the oldest step), t1 [N-1][ns^2] keeps T1_k between the two passes.  N ns + (2 N - 1) ns^2 doubles per instance.
+struct DirectWindow {
+    double* x = nullptr;
+    double* cov = nullptr;
+    double* t1 = nullptr;
 };
 
 // Lambda^-1 from Lambda (both NS x NS row-major in LDS), through the symmetrically scaled matrix D Lambda D with D = diag(Lambda_ii^-1/2),
@@ -99,9 +117,15 @@ DEKF_FN bool direct_inverse(const double* Lam, double* Li, double* d, double* sc
 // The direct solve of instance b over window steps kstart .. kstart + K - 1 (K >= 2): writes x_mhe, v_b, the status words and
 // cov[b] = Cov(x_T) ([B][NS][NS]).  sm: DirectScratch::len(NS) doubles of LDS.  Returns false for a non-positive or non-finite
 // pivot or a non-finite result (status DEKF_SOLVE_NUMERIC).
-template <int L, int FT>
-DEKF_FN bool direct_solve_t(const DevCfg& c, const DevState& s, int b, int kstart, int K, double* sm, double* cov) {
+// SMOOTH: also the window smoother; win's stores receive x_k and Cov(x_k) of all K window steps, k = 0 the oldest, or NaN in all K
+// entries of both when the result is false.  No more LDS than without: the backward pass lives in what the forward pass left dead.
+template <int L, int FT, bool SMOOTH = false>
+DEKF_FN bool direct_solve_t(const DevCfg& c, const DevState& s, int b, int kstart, int K, double* sm, double* cov, DirectWindow win = DirectWindow()) {
     constexpr int NM = 3 * L, NS = 9 + NM * FT, NS2 = NS * NS;
+    // this instance's stores (SMOOTH only): u_k then x_k | Li_k then P_k | T1_k
+    double* const xw = SMOOTH ? win.x + (size_t)b * c.N * NS : nullptr;
+    double* const cw = SMOOTH ? win.cov + (size_t)b * c.N * NS2 : nullptr;
+    double* const tw = SMOOTH ? win.t1 + (size_t)b * (c.N - 1) * NS2 : nullptr;
     double* M = sm;
     double* h = M + NS2;
     double* Lam = h + NS;
@@ -227,11 +251,20 @@ DEKF_FN bool direct_solve_t(const DevCfg& c, const DevState& s, int b, int kstar
                 double sub = 0.0;
                 for (int t = 0; t < NS; ++t) sub += T1[NS * i + t] * G[NS * j + t];
                 M[e] = acc - sub;
+                if constexpr (SMOOTH) {  // what the backward pass needs of step k
+                    cw[(size_t)NS2 * k + e] = Li[e];
+                    tw[(size_t)NS2 * k + e] = T1[e];
+                }
             } else {
                 const int i = e - NS2;
                 double acc = 0.0;
                 for (int t = 0; t < NS; ++t) acc += T1[NS * i + t] * r[t];
                 h[i] = acc - Qb[i];
+                if constexpr (SMOOTH) {  // u_k = Lambda^-1 r
+                    double u = 0.0;
+                    for (int t = 0; t < NS; ++t) u += Li[NS * i + t] * r[t];
+                    xw[NS * k + i] = u;
+                }
             }
         });
     }
@@ -266,6 +299,62 @@ DEKF_FN bool direct_solve_t(const DevCfg& c, const DevState& s, int b, int kstar
         s.dua_res[b] = NAN;
     }
     DEKF_SYNC();
+    if constexpr (SMOOTH) {
+        if (!finite) {  // group-uniform: never a stale or half-written trajectory
+            wfor(K * (NS2 + NS), [&](int e) {
+                if (e < K * NS2) cw[e] = NAN;
+                else xw[e - K * NS2] = NAN;
+            });
+            return false;
+        }
+        // The backward pass.  M, Lambda, G, T1 and Lambda^-1 of the forward pass are dead: P_{k+1} stays where the newest block's
+        // Lambda^-1 is, x_{k+1} alternates between the two halves of T1's head (x_T is in the first), and step k's operands take the rest.
+        double* P = Li;
+        double* Lk = M;    // Li_k
+        double* Tk = G;    // T1_k
+        double* W = Lam;   // T1_k' P_{k+1}
+        double* xn = x;    // x_{k+1}
+        double* xo = x + NS;
+        wfor(NS2 + NS, [&](int e) {  // the newest block: the values x_mhe and cov were written from
+            if (e < NS2) cw[(size_t)NS2 * (K - 1) + e] = P[e];
+            else xw[NS * (K - 1) + e - NS2] = xn[e - NS2];
+        });
+        for (int k = K - 2; k >= 0; --k) {
+            const double* const uk = xw + NS * k;
+            double* const ck = cw + (size_t)NS2 * k;
+            const double* const tk = tw + (size_t)NS2 * k;
+            wfor(NS2, [&](int e) {
+                Tk[e] = tk[e];
+                Lk[e] = ck[e];
+            });
+            wfor(NS2 + NS, [&](int e) {
+                if (e < NS2) {
+                    const int i = e / NS, j = e - NS * i;
+                    double acc = 0.0;
+                    for (int t = 0; t < NS; ++t) acc += Tk[NS * t + i] * P[NS * t + j];
+                    W[e] = acc;
+                } else {
+                    const int i = e - NS2;
+                    double acc = uk[i];
+                    for (int t = 0; t < NS; ++t) acc += Tk[NS * t + i] * xn[t];
+                    xo[i] = acc;
+                    xw[NS * k + i] = acc;
+                }
+            });
+            // P_k from its upper triangle, mirrored: symmetric to the bit
+            wfor(NS2, [&](int e) {
+                const int ie = e / NS, je = e - NS * ie;
+                const int i = ie < je ? ie : je, j = ie < je ? je : ie;
+                double acc = Lk[NS * i + j];
+                for (int t = 0; t < NS; ++t) acc += W[NS * i + t] * Tk[NS * t + j];
+                ck[e] = acc;
+                P[e] = acc;  // (this phase reads W, not P)
+            });
+            double* const sw = xn;
+            xn = xo;
+            xo = sw;
+        }
+    }
     return finite;
 }
 

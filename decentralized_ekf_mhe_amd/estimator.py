@@ -48,10 +48,12 @@ def _torch_runtime_first():
 
 
 class BatchedEstimator:
-    def __init__(self, params: DekfParams, batch: int, device: int = 0, stream=None, warm_start: bool = False, solver: str = "admm"):
+    def __init__(self, params: DekfParams, batch: int, device: int = 0, stream=None, warm_start: bool = False, solver: str = "admm",
+                 smoother: bool = False):
         """warm_start: full-window solves start from the previous tick's shifted solution (dekf_set_warm_start; off by default).
         solver: "admm" (default, the reference's OSQP-style ADMM) or "direct" (the exact optimum of the window QP and its covariance,
-        dekf_set_solver; see mhe_cov)"""
+        dekf_set_solver; see mhe_cov)
+        smoother: a direct handle also leaves every state of the window and its covariance (dekf_set_smoother; see window)"""
         if solver not in ("admm", "direct"):
             raise ValueError(f"solver must be 'admm' or 'direct', not {solver!r}")
         _torch_runtime_first()
@@ -66,6 +68,8 @@ class BatchedEstimator:
         try:
             if solver == "direct":
                 capi.check(self.lib.dekf_set_solver(self.h, capi.DEKF_SOLVER_DIRECT))
+            if smoother:
+                capi.check(self.lib.dekf_set_smoother(self.h, 1))
             if warm_start:
                 capi.check(self.lib.dekf_set_warm_start(self.h, 1))
         except capi.DekfError:
@@ -187,6 +191,15 @@ class BatchedEstimator:
         Cm = np.zeros((self.batch, ns, ns))
         capi.check(self.lib.dekf_get_mhe_cov(self.h, C.c_void_p(Cm.ctypes.data), capi.DEKF_HOST))
         return Cm
+
+    def window(self):
+        """(K, x_win [B, K, ns], cov_win [B, K, ns, ns]) of the last update of a smoothing handle (dekf_get_window): the K = min(T + 1, N)
+        states of the window it solved, oldest first, and their covariances"""
+        ns, N = self.params.dim_state, self.params.N
+        xw, cw = np.zeros((self.batch, N, ns)), np.zeros((self.batch, N, ns, ns))
+        K = C.c_int(0)
+        capi.check(self.lib.dekf_get_window(self.h, C.byref(K), C.c_void_p(xw.ctypes.data), C.c_void_p(cw.ctypes.data), capi.DEKF_HOST))
+        return K.value, xw[:, :K.value].copy(), cw[:, :K.value].copy()
 
     def kf_cov(self):
         ns = self.params.dim_state

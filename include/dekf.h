@@ -286,6 +286,33 @@ dekf_status dekf_get_warm_status(dekf_handle h, int* warm, dekf_mem where);
 dekf_status dekf_set_solver(dekf_handle h, int solver);
 dekf_status dekf_get_mhe_cov(dekf_handle h, double* cov, dekf_mem where); /* cov[B][ns][ns], row-major */
 
+/* ---- window smoother (opt-in, direct handles): every state of the window and its covariance -------------------------
+ * Adding these two symbols does not change DEKF_ABI_VERSION: dekf_params is untouched, and a caller that never calls them gets
+ * exactly the results (and bits) of before.
+ * dekf_set_smoother(h, on), on = 0 (default) or 1.  Allowed before dekf_initialize or right after dekf_reset (else DEKF_ERR_ORDER);
+ * the setting survives dekf_reset.  DEKF_ERR_INVALID for a null handle, any other `on`, and on = 1 on a handle that is not a direct
+ * handle (ADMM, KF).  dekf_set_solver(h, DEKF_SOLVER_ADMM) on a smoothing handle switches the smoother off with the direct solve
+ * (going back to DEKF_SOLVER_DIRECT does not switch it on again).  The first enable allocates the stores: N ns + (2 N - 1) ns^2
+ * doubles per instance (ns = dim_state; Go1 27 KB, PogoX with N = 100 136 KB, Go1 with foot states 141 KB).
+ * A smoothing handle's update runs the backward (Rauch-Tung-Striebel) recursion behind the direct solve's forward elimination, in the
+ * same kernel launch, and leaves, per instance, for the K = min(T + 1, N) steps of the window it solved (window-fill and full windows):
+ *  - x_win[b][k][:], k = 0 (oldest, step T - K + 1) .. K - 1 (newest, step T): the state blocks of the minimiser of the QP the direct
+ *    solve minimises (equality rows held, +-1e30 rows free, the ADMM path's arrival cost);
+ *  - cov_win[b][k][:][:] = Cov(x_k) = [J^-1]_kk, row-major and symmetric to the bit for k < K - 1, J the information matrix of the
+ *    window's states (the J whose last diagonal block dekf_get_mhe_cov returns);
+ *  - x_mhe, v_b, status, solver info and dekf_get_mhe_cov are bit-identical to the same handle with the smoother off; x_win[b][K-1]
+ *    is bit-identical to x_mhe[b] and cov_win[b][K-1] to the covariance of dekf_get_mhe_cov;
+ *  - an instance whose status is DEKF_SOLVE_NUMERIC gets NaN in all K entries of both arrays; its neighbours are unaffected.
+ *  - dekf_solve_kernel_name names the direct kernel's smoothing twin (k_mhe_solve_direct_*_smooth) for both window kinds.
+ * dekf_get_window: x_win[B][N][dim_state], cov_win[B][N][dim_state][dim_state]; entries k >= K are not written.  *steps (always a host
+ * int*) receives K of the last update.  Any of the three pointers may be NULL.  Host pointers: copy and synchronise, like
+ * dekf_get_mhe_cov; device pointers: in stream order.  DEKF_ERR_INVALID on a handle without the smoother, DEKF_ERR_ORDER before the
+ * first update and after dekf_reset until the next update.
+ * Not part of this interface: the lag-one cross-covariances Cov(x_k, x_{k+1}) (one product away from what the backward pass holds),
+ * and the window of an ADMM handle. */
+dekf_status dekf_set_smoother(dekf_handle h, int on);
+dekf_status dekf_get_window(dekf_handle h, int* steps, double* x_win, double* cov_win, dekf_mem where);
+
 /* status[B] values written by dekf_update */
 #define DEKF_SOLVE_NONE 0       /* no solve yet (T = 0) */
 #define DEKF_SOLVE_OK 1         /* OSQP_SOLVED */

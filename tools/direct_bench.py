@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
-"""Cold ADMM, warm ADMM (dekf_set_warm_start) and the direct solve (dekf_set_solver(h, DEKF_SOLVER_DIRECT)) on the four BASELINE
-shapes: Go1 B=4096, Cassie B=4096, PogoX B=1024 (N = 100) and Go1 with foot-position states (leg_odom_type 1) B=4096.  One JSON line
-per shape, the three modes side by side, each with
+"""Cold ADMM, warm ADMM (dekf_set_warm_start), the direct solve (dekf_set_solver(h, DEKF_SOLVER_DIRECT)) and the direct solve with the
+window smoother (dekf_set_smoother; mode direct_smooth) on the four BASELINE shapes: Go1 B=4096, Cassie B=4096, PogoX B=1024 (N = 100)
+and Go1 with foot-position states (leg_odom_type 1) B=4096.  One JSON line per shape, the modes side by side, each with
   steps_per_s   over `steps` timed steps after the window has filled (device-resident logs, the loop of tools/warm_start_bench.py)
   solve_ms      average launch time of the MHE solve (timing class 2, HIP events), in a second pass over the same steps
   assemble_ms   average launch time of the term construction (timing class 1: k_mhe_assemble), same pass
   kernel        the full-window solve kernel
-and appends them to profiles/r08_direct_bench.jsonl (--out).  Timing class 1 and 2 events are only on in the second pass, so
-steps_per_s is measured without them.
-    python tools/direct_bench.py [shape ...] [--steps 200] [--out profiles/r08_direct_bench.jsonl]"""
+and appends them to profiles/r08_direct_bench.jsonl, or to profiles/r09_smoother_bench.jsonl when direct_smooth is among the modes
+(--out).  Timing class 1 and 2 events are only on in the second pass, so steps_per_s is measured without them.  --repeat R measures the
+modes R times in turn (direct, direct_smooth, direct, direct_smooth, ...) and reports each mode's best steps_per_s and lowest solve_ms
+with the list of all of them: the modes alternate inside one process, so that a drift of the machine does not land on one of them.
+    python tools/direct_bench.py [shape ...] [--steps 200] [--modes cold,warm,direct] [--repeat 1] [--out FILE]
+    python tools/direct_bench.py --modes direct,direct_smooth --repeat 3          # the smoother against its yardstick"""
 import argparse
 import json
 import os
@@ -30,7 +33,8 @@ SHAPES = {
     "pogox": (pogox_params, 1024, {}),
     "go1_foot": (go1_params, 4096, {"leg_odom_type": 1}),
 }
-MODES = {"cold": dict(), "warm": dict(warm_start=True), "direct": dict(solver="direct")}
+MODES = {"cold": dict(), "warm": dict(warm_start=True), "direct": dict(solver="direct"),
+         "direct_smooth": dict(solver="direct", smoother=True)}
 
 
 def one(p, B, sd, W, steps, mode):
@@ -73,8 +77,12 @@ def main():
     ap.add_argument("shapes", nargs="*", default=list(SHAPES))
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--modes", default="cold,warm,direct")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08_direct_bench.jsonl"))
+    ap.add_argument("--repeat", type=int, default=1)
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    modes = a.modes.split(",")
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "r09_smoother_bench.jsonl" if "direct_smooth" in modes else "r08_direct_bench.jsonl")
     for name in a.shapes:
         maker, B, kw = SHAPES[name]
         p = maker()
@@ -84,10 +92,22 @@ def main():
         W = max(p.N + 10, 64)  # (as tools/bench_shapes.py: past the window fill and the first vision intervals)
         sd = streams_to_device(make_streams(p, B, W + a.steps))
         line = {"shape": name, "batch": B, "N": int(p.N), "steps": a.steps}
-        for mode in a.modes.split(","):
-            line[mode] = one(p, B, sd, W, a.steps, mode)
+        runs = {mode: [] for mode in modes}
+        for _ in range(a.repeat):
+            for mode in modes:
+                runs[mode].append(one(p, B, sd, W, a.steps, mode))
+        for mode in modes:
+            best = dict(max(runs[mode], key=lambda r: r["steps_per_s"]))
+            best["solve_ms"] = min(r["solve_ms"] for r in runs[mode])
+            if a.repeat > 1:
+                best["all_steps_per_s"] = [r["steps_per_s"] for r in runs[mode]]
+                best["all_solve_ms"] = [r["solve_ms"] for r in runs[mode]]
+            line[mode] = best
         if "direct" in line:
             line.update({f"direct_over_{m}": line["direct"]["steps_per_s"] / line[m]["steps_per_s"] for m in ("cold", "warm") if m in line})
+        if "direct" in line and "direct_smooth" in line:
+            line["smooth_solve_ms_over_direct"] = line["direct_smooth"]["solve_ms"] / line["direct"]["solve_ms"]
+            line["smooth_steps_per_s_over_direct"] = line["direct_smooth"]["steps_per_s"] / line["direct"]["steps_per_s"]
         print(json.dumps(line), flush=True)
         if a.out:
             with open(a.out, "a") as f:
