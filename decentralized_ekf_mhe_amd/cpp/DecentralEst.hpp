@@ -107,6 +107,9 @@ struct robot_params {
     // new: the window smoother of the direct solve: every state of the window and its covariance in x_window_ / C_window_ after
     // every update (dekf_set_smoother; needs directSolve_)
     bool smoothWindow_ = false;
+    // new: the cross-covariances of that window: Cov(x_k, x_{k+1}) in C_lag1_ and Cov(x_k, x_T) in C_newest_ after every update
+    // (dekf_set_window_cross; needs smoothWindow_)
+    bool windowCross_ = false;
 };
 
 // ---- DecentralEst.hpp:65-94 ----------------------------------------------------------------
@@ -195,6 +198,10 @@ class DecentralizedEstimation {
         if (direct_) dekf_shim::check(dekf_set_solver(h_, DEKF_SOLVER_DIRECT));
         smooth_ = params->smoothWindow_ && prm_.est_type == 0;
         if (smooth_) dekf_shim::check(dekf_set_smoother(h_, 1));
+        cross_ = params->windowCross_ && prm_.est_type == 0;
+        if (cross_) dekf_shim::check(dekf_set_window_cross(h_, 1));
+        C_lag1_.clear();
+        C_newest_.clear();
         window_steps_ = 0;
         x_window_.clear();
         C_window_.clear();
@@ -227,6 +234,21 @@ class DecentralizedEstimation {
                     for (size_t j = 0; j < ns; ++j) C_window_[k]((int)i, (int)j) = win_C_[ns * ns * k + ns * i + j];
                 }
         }
+        if (cross_) {
+            const size_t ns = (size_t)dim_state_, N = (size_t)prm_.N;
+            win_L_.resize((N - 1) * ns * ns);
+            win_Z_.resize(N * ns * ns);
+            int K = 0;
+            dekf_shim::check(dekf_get_window_cross(h_, &K, win_L_.data(), win_Z_.data(), DEKF_HOST));
+            C_lag1_.assign((size_t)K - 1, MatrixXd(dim_state_, dim_state_));
+            C_newest_.assign((size_t)K, MatrixXd(dim_state_, dim_state_));
+            for (size_t k = 0; k < (size_t)K; ++k)
+                for (size_t i = 0; i < ns; ++i)
+                    for (size_t j = 0; j < ns; ++j) {
+                        if (k + 1 < (size_t)K) C_lag1_[k]((int)i, (int)j) = win_L_[ns * ns * k + ns * i + j];
+                        C_newest_[k]((int)i, (int)j) = win_Z_[ns * ns * k + ns * i + j];
+                    }
+        }
     }
     // DecentralEst.cpp:1011-1015
     void reset() { if (h_) dekf_shim::check(dekf_reset(h_)); }
@@ -245,6 +267,10 @@ class DecentralizedEstimation {
     int window_steps_ = 0;
     std::vector<VectorXd> x_window_;
     std::vector<MatrixXd> C_window_;
+    // new: the cross-covariances of that window (robot_params::windowCross_): C_lag1_[k] = Cov(x_k, x_{k+1}), window_steps_ - 1 of them,
+    // and C_newest_[k] = Cov(x_k, x_T), window_steps_ of them; rows index x_k
+    std::vector<MatrixXd> C_lag1_;
+    std::vector<MatrixXd> C_newest_;
     int solver_status_ = DEKF_SOLVE_NONE, solver_iters_ = 0;  // new: the reference ignores OSQP's flag
     int dim_state_ = 9;                                       // 9 + 3 * leg_odom_type * num_legs
     // new: take raw Go1 joint states from robot_store (joint_states_position_/velocity_) instead of
@@ -258,7 +284,8 @@ class DecentralizedEstimation {
     dekf_handle h_ = nullptr;
     bool direct_ = false;  // robot_params::directSolve_ on an MHE handle
     bool smooth_ = false;  // robot_params::smoothWindow_ on an MHE handle
-    std::vector<double> win_x_, win_C_;
+    bool cross_ = false;   // robot_params::windowCross_ on an MHE handle
+    std::vector<double> win_x_, win_C_, win_L_, win_Z_;
 
     // what GetMeasurement reads from robot_store by pointer (DecentralEst.cpp:867-879)
     void latch() {

@@ -33,7 +33,8 @@ __global__ void k_mhe_marginalize_early(DevCfg c, DevState s, int T);
 // the direct solve kernels (direct_kernels.def)
 #define DEKF_DIRECT_KERNEL(NAME, ...)                                               \
     __global__ void NAME(DevCfg c, DevState s, int kstart, int K, double* cov);   \
-    __global__ void NAME##_smooth(DevCfg c, DevState s, int kstart, int K, double* cov, DirectWindow win);
+    __global__ void NAME##_smooth(DevCfg c, DevState s, int kstart, int K, double* cov, DirectWindow win); \
+    __global__ void NAME##_smooth_cross(DevCfg c, DevState s, int kstart, int K, double* cov, DirectWindow win, DirectCross cross);
 #include "direct_kernels.def"
 __global__ void k_gap();
 __global__ void k_kf_initialize(DevCfg c, DevState s);
@@ -88,6 +89,10 @@ struct dekf_handle_s {
     bool smoother = false;
     DirectWindow win;
     int win_steps = 0;
+    // dekf_set_window_cross: a cross handle (a smoothing handle with the option) launches direct->fn_cross, whose backward pass turns
+    // win.t1's entries into Cov(x_k, x_{k+1}) and leaves Cov(x_k, x_T) in cross_st.newest (mhe_direct_core.h: DirectCross)
+    bool cross = false;
+    DirectCross cross_st;
     size_t lds_solve = 0, lds_asm = 0, lds_kf = 0;
     int ekf_count = 0, pushes = 0, next_T = 0;
     bool initialized = false;
@@ -180,14 +185,18 @@ const SolveKernel* solve_kernel(SolveRole role, int L, int N) {
 // The direct solve kernels as dekf_set_solver selects them: every row of direct_kernels.def
 typedef void (*DirectFn)(DevCfg, DevState, int, int, double*);
 typedef void (*DirectSmoothFn)(DevCfg, DevState, int, int, double*, DirectWindow);
+typedef void (*DirectCrossFn)(DevCfg, DevState, int, int, double*, DirectWindow, DirectCross);
 struct DirectKernel {
     int legs, ft, nfix;  // direct_solve_t's L and FT; the horizon the row is meant for (0: any)
     DirectFn fn;
     const char* name;
     DirectSmoothFn fn_smooth;  // the smoothing twin (dekf_set_smoother)
     const char* name_smooth;
+    DirectCrossFn fn_cross;  // the twin with the window cross-covariances (dekf_set_window_cross)
+    const char* name_cross;
 };
-#define DEKF_DIRECT_KERNEL(NAME, L, FT, NFIX) {L, FT, NFIX, NAME, #NAME, NAME##_smooth, #NAME "_smooth"},
+#define DEKF_DIRECT_KERNEL(NAME, L, FT, NFIX) \
+    {L, FT, NFIX, NAME, #NAME, NAME##_smooth, #NAME "_smooth", NAME##_smooth_cross, #NAME "_smooth_cross"},
 const DirectKernel direct_kernels[] = {
 #include "direct_kernels.def"
 };
@@ -552,7 +561,7 @@ dekf_status dekf_reset(dekf_handle h) {
     h->pushes = 0;
     h->next_T = 0;
     h->initialized = false;
-    h->mhe_cov_valid = false;  // (the solver and smoother settings survive)
+    h->mhe_cov_valid = false;  // (the solver, smoother and cross settings survive)
     h->win_steps = 0;
     return DEKF_OK;
 }
@@ -721,7 +730,9 @@ dekf_status dekf_update(dekf_handle h, int T) {
             { static const int gap = getenv("DEKF_DEBUG_GAP_KERNEL") ? atoi(getenv("DEKF_DEBUG_GAP_KERNEL")) : 0;
               for (int i = 0; i < gap; ++i) k_gap<<<1, 64, 0, ss>>>(); }
 #endif
-            if (h->solver == DEKF_SOLVER_DIRECT && h->smoother)
+            if (h->solver == DEKF_SOLVER_DIRECT && h->smoother && h->cross)
+                h->direct->fn_cross<<<h->c.B, 64, h->lds_direct, ss>>>(h->c, sp, kstart, K, h->mhe_cov, h->win, h->cross_st);
+            else if (h->solver == DEKF_SOLVER_DIRECT && h->smoother)
                 h->direct->fn_smooth<<<h->c.B, 64, h->lds_direct, ss>>>(h->c, sp, kstart, K, h->mhe_cov, h->win);
             else if (h->solver == DEKF_SOLVER_DIRECT)
                 h->direct->fn<<<h->c.B, 64, h->lds_direct, ss>>>(h->c, sp, kstart, K, h->mhe_cov);
@@ -896,7 +907,7 @@ dekf_status dekf_set_solver(dekf_handle h, int solver) {
     }
     h->solver = solver;
     h->mhe_cov_valid = false;
-    if (solver == DEKF_SOLVER_ADMM) h->smoother = false;  // the smoother is the direct solve's: switched off with it
+    if (solver == DEKF_SOLVER_ADMM) h->smoother = h->cross = false;  // the smoother and its cross-covariances are the direct solve's
     h->win_steps = 0;
     return DEKF_OK;
 }
@@ -917,6 +928,25 @@ dekf_status dekf_set_smoother(dekf_handle h, int on) {
         h->win.t1 = h->win.cov + B * N * ns * ns;
     }
     h->smoother = on != 0;
+    if (!on) h->cross = false;  // the cross-covariances are the smoother's: switched off with it
+    h->win_steps = 0;
+    return DEKF_OK;
+}
+
+dekf_status dekf_set_window_cross(dekf_handle h, int on) {
+    if (!h) return fail(DEKF_ERR_INVALID, "null handle");
+    if (on != 0 && on != 1) return fail(DEKF_ERR_INVALID, "dekf_set_window_cross: on must be 0 or 1");
+    if (on && !h->smoother) return fail(DEKF_ERR_INVALID, "the window cross-covariances need a smoothing handle (dekf_set_smoother(h, 1))");
+    if (h->initialized) return fail(DEKF_ERR_ORDER, "dekf_set_window_cross is allowed before dekf_initialize or right after dekf_reset");
+    if (on && !h->cross_st.newest) {
+        HIPCHK(hipSetDevice(h->device));
+        const size_t B = (size_t)h->c.B, N = (size_t)h->c.N, ns = (size_t)h->c.ns;
+        double* st = nullptr;  // (the lag-one blocks take the smoother's t1 store)
+        HIPCHK(hipMalloc(&st, B * N * ns * ns * sizeof(double)));
+        h->blocks.push_back(st);
+        h->cross_st.newest = st;
+    }
+    h->cross = on != 0;
     h->win_steps = 0;
     return DEKF_OK;
 }
@@ -939,6 +969,26 @@ dekf_status dekf_get_window(dekf_handle h, int* steps, double* x_win, double* co
         if (cov_win) HIPCHK(hipMemcpy2DAsync(cov_win, N * ns * ns * 8, h->win.cov, N * ns * ns * 8, K * ns * ns * 8, B, kind, h->stream));
     }
     if (where == DEKF_HOST && (x_win || cov_win)) HIPCHK(hipStreamSynchronize(h->stream));
+    return DEKF_OK;
+}
+
+dekf_status dekf_get_window_cross(dekf_handle h, int* steps, double* cov_lag1, double* cov_newest, dekf_mem where) {
+    if (!h) return fail(DEKF_ERR_INVALID, "null handle");
+    if (!h->cross) return fail(DEKF_ERR_INVALID, "dekf_get_window_cross needs a cross handle (dekf_set_window_cross(h, 1))");
+    if (!h->win_steps) return fail(DEKF_ERR_ORDER, "dekf_get_window_cross before the first update (since dekf_create or dekf_reset)");
+    const size_t B = (size_t)h->c.B, N = (size_t)h->c.N, n2 = (size_t)h->c.ns * h->c.ns, K = (size_t)h->win_steps;
+    if (steps) *steps = h->win_steps;
+    // the K - 1 and K written entries of every instance: [B][N - 1][ns^2] and [B][N][ns^2], the pitch the same on both sides
+    const hipMemcpyKind kind = where == DEKF_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (K == N) {  // full windows: one contiguous copy each
+        dekf_status st;
+        if ((st = fetch(h, cov_lag1, h->win.t1, B * (N - 1) * n2 * 8, where))) return st;
+        if ((st = fetch(h, cov_newest, h->cross_st.newest, B * N * n2 * 8, where))) return st;
+    } else {
+        if (cov_lag1) HIPCHK(hipMemcpy2DAsync(cov_lag1, (N - 1) * n2 * 8, h->win.t1, (N - 1) * n2 * 8, (K - 1) * n2 * 8, B, kind, h->stream));
+        if (cov_newest) HIPCHK(hipMemcpy2DAsync(cov_newest, N * n2 * 8, h->cross_st.newest, N * n2 * 8, K * n2 * 8, B, kind, h->stream));
+    }
+    if (where == DEKF_HOST && (cov_lag1 || cov_newest)) HIPCHK(hipStreamSynchronize(h->stream));
     return DEKF_OK;
 }
 
@@ -1011,7 +1061,7 @@ dekf_status dekf_launch_info(dekf_handle h, int* solve_workgroups, int* compute_
 
 const char* dekf_solve_kernel_name(dekf_handle h, int full_window) {
     if (!h || h->c.est_type != 0) return nullptr;
-    if (h->solver == DEKF_SOLVER_DIRECT) return h->smoother ? h->direct->name_smooth : h->direct->name;
+    if (h->solver == DEKF_SOLVER_DIRECT) return h->cross ? h->direct->name_cross : h->smoother ? h->direct->name_smooth : h->direct->name;
     return (full_window && h->solve_kernel_full) ? h->solve_name_full : h->solve_name;
 }
 

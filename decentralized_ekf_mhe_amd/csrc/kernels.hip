@@ -198,6 +198,8 @@ __global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_marginalize_early(De
 // instance queue of the ADMM kernels would gain nothing.  cov: Cov(x_T) per instance, [B][ns][ns].
 // Every row also defines its smoothing twin NAME_smooth (dekf_set_smoother): direct_solve_t's SMOOTH instantiation, the backward pass
 // in the same launch; win: the window stores (mhe_direct_core.h: DirectWindow).  NAME itself is the instantiation it was.
+// And the twin of that, NAME_smooth_cross (dekf_set_window_cross): the CROSS instantiation, whose backward pass also leaves the lag-one and
+// to-newest cross-covariances; cross: the store of the latter (DirectCross).  NAME and NAME_smooth are the instantiations they were.
 #define DEKF_DIRECT_KERNEL(NAME, L, FT, NFIX)                                                                                 \
     __global__ void __launch_bounds__(64) NAME(DevCfg c, DevState s, int kstart, int K, double* cov) {                         \
         extern __shared__ double lds[];                                                                                      \
@@ -206,13 +208,19 @@ __global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_marginalize_early(De
     __global__ void __launch_bounds__(64) NAME##_smooth(DevCfg c, DevState s, int kstart, int K, double* cov, DirectWindow win) { \
         extern __shared__ double lds[];                                                                                      \
         direct_solve_t<L, FT, true>(c, s, blockIdx.x, kstart, K, lds, cov, win);                                              \
+    }                                                                                                                        \
+    __global__ void __launch_bounds__(64) NAME##_smooth_cross(DevCfg c, DevState s, int kstart, int K, double* cov, DirectWindow win, \
+                                                              DirectCross cross) {                                           \
+        extern __shared__ double lds[];                                                                                      \
+        direct_solve_t<L, FT, true, true>(c, s, blockIdx.x, kstart, K, lds, cov, win, cross);                                 \
     }
 #ifdef DEKF_KSET_ONLY
 #define DEKF_DIRECT_KERNEL_OFF(...)
 #else
 #define DEKF_DIRECT_KERNEL_OFF(NAME, ...)                               \
     __global__ void NAME(DevCfg, DevState, int, int, double*) {}        \
-    __global__ void NAME##_smooth(DevCfg, DevState, int, int, double*, DirectWindow) {}
+    __global__ void NAME##_smooth(DevCfg, DevState, int, int, double*, DirectWindow) {} \
+    __global__ void NAME##_smooth_cross(DevCfg, DevState, int, int, double*, DirectWindow, DirectCross) {}
 #endif
 #include "direct_kernels.def"
 

@@ -25,6 +25,13 @@
 // the first two into x_k and P_k in place, x_{k+1} and P_{k+1} staying in LDS.  The forward pass and everything it writes are the same
 // instructions on the same values with and without SMOOTH.
 //
+// The window cross-covariances (CROSS, dekf_set_window_cross; SMOOTH only): x_k = u_k + T1_k' x_{k+1} + e_k with e_k independent of every
+// later state, so
+//     W_k = Cov(x_k, x_{k+1}) = T1_k' P_{k+1}                                    (lag-one: the W of the P_k recursion)
+//     Z_{K-1} = P_{K-1}      Z_k = Cov(x_k, x_T) = T1_k' Z_{k+1}                 (to-newest: one more product per step)
+// W_k goes back over T1_k in its store (t1[k] is dead once step k has loaded it), Z_k into a store of its own (DirectCross).  The P_k
+// recursion keeps its operations and their order: everything SMOOTH writes has the same bits with and without CROSS.
+//
 // Inputs are exactly what solve_window_t reads: the window records at ring slot (kstart + k) % wcap (Meas from Rec::BM / qm, Dyn
 // from Rec::AS / QD and the bias gains, VO gains from Rec::QC) and, from the solve's input snapshot (DevState::snap), the arrival
 // cost and the VO flag / bound of every slot.  Qd | Qc of the newest record are never read (k_mhe_marginalize_early of the next step
@@ -49,6 +56,13 @@ struct DirectWindow {
     double* x = nullptr;
     double* cov = nullptr;
     double* t1 = nullptr;
+};
+
+// The cross-covariance stores (dekf_set_window_cross), [B][...] each: lag-one Cov(x_k, x_{k+1}) [N-1][ns^2] is DirectWindow::t1 itself,
+// which the backward pass of a CROSS instantiation overwrites in place; newest [N][ns^2] receives Cov(x_k, x_T).  N ns^2 more doubles
+// per instance.
+struct DirectCross {
+    double* newest = nullptr;
 };
 
 // Lambda^-1 from Lambda (both NS x NS row-major in LDS), through the symmetrically scaled matrix D Lambda D with D = diag(Lambda_ii^-1/2),
@@ -119,13 +133,18 @@ DEKF_FN bool direct_inverse(const double* Lam, double* Li, double* d, double* sc
 // pivot or a non-finite result (status DEKF_SOLVE_NUMERIC).
 // SMOOTH: also the window smoother; win's stores receive x_k and Cov(x_k) of all K window steps, k = 0 the oldest, or NaN in all K
 // entries of both when the result is false.  No more LDS than without: the backward pass lives in what the forward pass left dead.
-template <int L, int FT, bool SMOOTH = false>
-DEKF_FN bool direct_solve_t(const DevCfg& c, const DevState& s, int b, int kstart, int K, double* sm, double* cov, DirectWindow win = DirectWindow()) {
+// CROSS (with SMOOTH): also the cross-covariances; win.t1's K - 1 first entries end as Cov(x_k, x_{k+1}) and cross.newest's K first
+// entries receive Cov(x_k, x_T), or NaN in all of them when the result is false.  Still no more LDS.
+template <int L, int FT, bool SMOOTH = false, bool CROSS = false>
+DEKF_FN bool direct_solve_t(const DevCfg& c, const DevState& s, int b, int kstart, int K, double* sm, double* cov, DirectWindow win = DirectWindow(),
+                            DirectCross cross = DirectCross()) {
+    static_assert(SMOOTH || !CROSS, "the cross-covariances come out of the smoother's backward pass");
     constexpr int NM = 3 * L, NS = 9 + NM * FT, NS2 = NS * NS;
     // this instance's stores (SMOOTH only): u_k then x_k | Li_k then P_k | T1_k
     double* const xw = SMOOTH ? win.x + (size_t)b * c.N * NS : nullptr;
     double* const cw = SMOOTH ? win.cov + (size_t)b * c.N * NS2 : nullptr;
     double* const tw = SMOOTH ? win.t1 + (size_t)b * (c.N - 1) * NS2 : nullptr;
+    double* const zw = CROSS ? cross.newest + (size_t)b * c.N * NS2 : nullptr;  // Z_k (CROSS only)
     double* M = sm;
     double* h = M + NS2;
     double* Lam = h + NS;
@@ -278,6 +297,7 @@ DEKF_FN bool direct_solve_t(const DevCfg& c, const DevState& s, int b, int kstar
             double acc = 0.0;
             for (int t = 0; t < NS; ++t) acc += Li[NS * i + t] * r[t];
             x[i] = acc;
+            if constexpr (CROSS) h[i] = acc;  // (h is dead: the backward pass keeps x_T there, T1's block goes to Z)
         }
     });
     bool finite = ok;
@@ -305,19 +325,36 @@ DEKF_FN bool direct_solve_t(const DevCfg& c, const DevState& s, int b, int kstar
                 if (e < K * NS2) cw[e] = NAN;
                 else xw[e - K * NS2] = NAN;
             });
+            if constexpr (CROSS) {
+                wfor((2 * K - 1) * NS2, [&](int e) {
+                    if (e < K * NS2) zw[e] = NAN;
+                    else tw[e - K * NS2] = NAN;
+                });
+            }
             return false;
         }
         // The backward pass.  M, Lambda, G, T1 and Lambda^-1 of the forward pass are dead: P_{k+1} stays where the newest block's
         // Lambda^-1 is, x_{k+1} alternates between the two halves of T1's head (x_T is in the first), and step k's operands take the rest.
+        // CROSS: x_{k+1} / x_k alternate between h and Qb instead (as dead as the rest), which leaves T1's whole block to Z_{k+1}; Z_k is
+        // written where W was once P_k has been formed, and the two blocks change roles every step.
         double* P = Li;
         double* Lk = M;    // Li_k
         double* Tk = G;    // T1_k
-        double* W = Lam;   // T1_k' P_{k+1}
-        double* xn = x;    // x_{k+1}
-        double* xo = x + NS;
+        double* W = Lam;   // T1_k' P_{k+1} (CROSS: then Z_k)
+        double* Zn = T1;   // Z_{k+1} (CROSS only)
+        (void)Zn;
+        double* xn = CROSS ? h : x;  // x_{k+1}
+        double* xo = CROSS ? Qb : x + NS;
         wfor(NS2 + NS, [&](int e) {  // the newest block: the values x_mhe and cov were written from
-            if (e < NS2) cw[(size_t)NS2 * (K - 1) + e] = P[e];
-            else xw[NS * (K - 1) + e - NS2] = xn[e - NS2];
+            if (e < NS2) {
+                cw[(size_t)NS2 * (K - 1) + e] = P[e];
+                if constexpr (CROSS) {  // Z_{K-1} = P_{K-1}: x_T is in h since the tail, nothing reads T1's head any more
+                    zw[(size_t)NS2 * (K - 1) + e] = P[e];
+                    Zn[e] = P[e];
+                }
+            } else {
+                xw[NS * (K - 1) + e - NS2] = xn[e - NS2];
+            }
         });
         for (int k = K - 2; k >= 0; --k) {
             const double* const uk = xw + NS * k;
@@ -333,6 +370,7 @@ DEKF_FN bool direct_solve_t(const DevCfg& c, const DevState& s, int b, int kstar
                     double acc = 0.0;
                     for (int t = 0; t < NS; ++t) acc += Tk[NS * t + i] * P[NS * t + j];
                     W[e] = acc;
+                    if constexpr (CROSS) tw[(size_t)NS2 * k + e] = acc;  // Cov(x_k, x_{k+1}) over T1_k, which this lane loaded
                 } else {
                     const int i = e - NS2;
                     double acc = uk[i];
@@ -350,9 +388,22 @@ DEKF_FN bool direct_solve_t(const DevCfg& c, const DevState& s, int b, int kstar
                 ck[e] = acc;
                 P[e] = acc;  // (this phase reads W, not P)
             });
-            double* const sw = xn;
+            double* sw = xn;
             xn = xo;
             xo = sw;
+            if constexpr (CROSS) {
+                // Z_k = T1_k' Z_{k+1}, W's product on Z_{k+1} (t ascending), over W
+                wfor(NS2, [&](int e) {
+                    const int i = e / NS, j = e - NS * i;
+                    double acc = 0.0;
+                    for (int t = 0; t < NS; ++t) acc += Tk[NS * t + i] * Zn[NS * t + j];
+                    W[e] = acc;
+                    zw[(size_t)NS2 * k + e] = acc;
+                });
+                sw = W;
+                W = Zn;
+                Zn = sw;
+            }
         }
     }
     return finite;

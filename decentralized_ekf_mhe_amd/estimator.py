@@ -47,13 +47,23 @@ def _torch_runtime_first():
               file=sys.stderr)
 
 
+def relative_cov(cov_win, cov_newest, k):
+    """Cov(x_T - x_k) = P_T + P_k - Z_k - Z_k' of the window's newest state against its state k, from window()'s cov_win [..., K, ns, ns]
+    and window_cross()'s newest [..., K, ns, ns] (Z_k = Cov(x_k, x_T))"""
+    cov_win, cov_newest = np.asarray(cov_win), np.asarray(cov_newest)
+    Z = cov_newest[..., k, :, :]
+    return cov_win[..., -1, :, :] + cov_win[..., k, :, :] - Z - np.swapaxes(Z, -1, -2)
+
+
 class BatchedEstimator:
     def __init__(self, params: DekfParams, batch: int, device: int = 0, stream=None, warm_start: bool = False, solver: str = "admm",
-                 smoother: bool = False):
+                 smoother: bool = False, cross: bool = False):
         """warm_start: full-window solves start from the previous tick's shifted solution (dekf_set_warm_start; off by default).
         solver: "admm" (default, the reference's OSQP-style ADMM) or "direct" (the exact optimum of the window QP and its covariance,
         dekf_set_solver; see mhe_cov)
-        smoother: a direct handle also leaves every state of the window and its covariance (dekf_set_smoother; see window)"""
+        smoother: a direct handle also leaves every state of the window and its covariance (dekf_set_smoother; see window)
+        cross: a smoothing handle also leaves the window's lag-one and to-newest cross-covariances (dekf_set_window_cross; see
+        window_cross).  It implies nothing else: without smoother=True the library refuses it"""
         if solver not in ("admm", "direct"):
             raise ValueError(f"solver must be 'admm' or 'direct', not {solver!r}")
         _torch_runtime_first()
@@ -70,6 +80,8 @@ class BatchedEstimator:
                 capi.check(self.lib.dekf_set_solver(self.h, capi.DEKF_SOLVER_DIRECT))
             if smoother:
                 capi.check(self.lib.dekf_set_smoother(self.h, 1))
+            if cross:
+                capi.check(self.lib.dekf_set_window_cross(self.h, 1))
             if warm_start:
                 capi.check(self.lib.dekf_set_warm_start(self.h, 1))
         except capi.DekfError:
@@ -200,6 +212,15 @@ class BatchedEstimator:
         K = C.c_int(0)
         capi.check(self.lib.dekf_get_window(self.h, C.byref(K), C.c_void_p(xw.ctypes.data), C.c_void_p(cw.ctypes.data), capi.DEKF_HOST))
         return K.value, xw[:, :K.value].copy(), cw[:, :K.value].copy()
+
+    def window_cross(self):
+        """(K, lag1 [B, K - 1, ns, ns], newest [B, K, ns, ns]) of the last update of a cross handle (dekf_get_window_cross):
+        lag1[b, k] = Cov(x_k, x_{k+1}) and newest[b, k] = Cov(x_k, x_T) of the window's K states, rows indexing x_k (see relative_cov)"""
+        ns, N = self.params.dim_state, self.params.N
+        l1, zn = np.zeros((self.batch, N - 1, ns, ns)), np.zeros((self.batch, N, ns, ns))
+        K = C.c_int(0)
+        capi.check(self.lib.dekf_get_window_cross(self.h, C.byref(K), C.c_void_p(l1.ctypes.data), C.c_void_p(zn.ctypes.data), capi.DEKF_HOST))
+        return K.value, l1[:, :K.value - 1].copy(), zn[:, :K.value].copy()
 
     def kf_cov(self):
         ns = self.params.dim_state

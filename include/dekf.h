@@ -308,10 +308,34 @@ dekf_status dekf_get_mhe_cov(dekf_handle h, double* cov, dekf_mem where); /* cov
  * int*) receives K of the last update.  Any of the three pointers may be NULL.  Host pointers: copy and synchronise, like
  * dekf_get_mhe_cov; device pointers: in stream order.  DEKF_ERR_INVALID on a handle without the smoother, DEKF_ERR_ORDER before the
  * first update and after dekf_reset until the next update.
- * Not part of this interface: the lag-one cross-covariances Cov(x_k, x_{k+1}) (one product away from what the backward pass holds),
- * and the window of an ADMM handle. */
+ * Not part of this interface: the window of an ADMM handle. */
 dekf_status dekf_set_smoother(dekf_handle h, int on);
 dekf_status dekf_get_window(dekf_handle h, int* steps, double* x_win, double* cov_win, dekf_mem where);
+
+/* ---- window cross-covariances (opt-in, smoothing handles): what ties two states of the window together ---------------
+ * Two more additive symbols: DEKF_ABI_VERSION and dekf_params are unchanged, and a caller that never calls them gets exactly the
+ * results (and bits) of before.
+ * dekf_set_window_cross(h, on), on = 0 (default) or 1.  Call order as for dekf_set_smoother: before dekf_initialize or right after
+ * dekf_reset (else DEKF_ERR_ORDER); the setting survives dekf_reset.  DEKF_ERR_INVALID for a null handle, any other `on`, and on = 1
+ * on a handle without the smoother.  dekf_set_smoother(h, 0) and dekf_set_solver(h, DEKF_SOLVER_ADMM) switch the option off; switching
+ * those back on does not switch it on again.  The first enable allocates the one new store: N ns^2 doubles per instance (Go1 13 KB,
+ * Go1 with foot states 71 KB); the lag-one blocks take the place of the smoother's own T1 store.
+ * A cross handle's update runs the smoothing kernel's twin (k_mhe_solve_direct_*_smooth_cross, which dekf_solve_kernel_name then names
+ * for both window kinds), whose backward pass also leaves, per instance, with K = min(T + 1, N) and J the information matrix of
+ * dekf_get_window:
+ *  - cov_lag1[b][k][:][:] = Cov(x_k, x_{k+1}) = [J^-1]_{k,k+1}, k = 0 .. K - 2: rows index x_k, columns x_{k+1}, row-major;
+ *  - cov_newest[b][k][:][:] = Cov(x_k, x_T) = [J^-1]_{k,K-1}, k = 0 .. K - 1: rows index x_k.  The covariance of the relative motion
+ *    follows as Cov(x_T - x_k) = cov_win[K-1] + cov_win[k] - cov_newest[k] - cov_newest[k]';
+ *  - x_mhe, v_b, status, solver info, dekf_get_mhe_cov, x_win and cov_win are bit-identical to the same handle with the option off;
+ *    cov_newest[b][K-1] is bit-identical to cov_win[b][K-1], and cov_newest[b][K-2] to cov_lag1[b][K-2];
+ *  - an instance whose status is DEKF_SOLVE_NUMERIC gets NaN in all written entries of both arrays; its neighbours are unaffected.
+ * dekf_get_window_cross: cov_lag1[B][N-1][dim_state][dim_state], cov_newest[B][N][dim_state][dim_state]; entries k >= K - 1 of the
+ * first and k >= K of the second are not written.  *steps (always a host int*) receives K of the last update.  Any of the three
+ * pointers may be NULL.  Host and device pointers as in dekf_get_window.  DEKF_ERR_INVALID on a handle without the option,
+ * DEKF_ERR_ORDER before the first update and after dekf_reset until the next update.
+ * Not part of this interface: Cov(x_j, x_k) of other pairs, and the window of an ADMM handle. */
+dekf_status dekf_set_window_cross(dekf_handle h, int on);
+dekf_status dekf_get_window_cross(dekf_handle h, int* steps, double* cov_lag1, double* cov_newest, dekf_mem where);
 
 /* status[B] values written by dekf_update */
 #define DEKF_SOLVE_NONE 0       /* no solve yet (T = 0) */

@@ -1,17 +1,20 @@
 #!/usr/bin/env python3
-"""Cold ADMM, warm ADMM (dekf_set_warm_start), the direct solve (dekf_set_solver(h, DEKF_SOLVER_DIRECT)) and the direct solve with the
-window smoother (dekf_set_smoother; mode direct_smooth) on the four BASELINE shapes: Go1 B=4096, Cassie B=4096, PogoX B=1024 (N = 100)
+"""Cold ADMM, warm ADMM (dekf_set_warm_start), the direct solve (dekf_set_solver(h, DEKF_SOLVER_DIRECT)), the direct solve with the
+window smoother (dekf_set_smoother; mode direct_smooth) and that with the window cross-covariances (dekf_set_window_cross; mode
+direct_cross) on the four BASELINE shapes: Go1 B=4096, Cassie B=4096, PogoX B=1024 (N = 100)
 and Go1 with foot-position states (leg_odom_type 1) B=4096.  One JSON line per shape, the modes side by side, each with
   steps_per_s   over `steps` timed steps after the window has filled (device-resident logs, the loop of tools/warm_start_bench.py)
   solve_ms      average launch time of the MHE solve (timing class 2, HIP events), in a second pass over the same steps
   assemble_ms   average launch time of the term construction (timing class 1: k_mhe_assemble), same pass
   kernel        the full-window solve kernel
-and appends them to profiles/r08_direct_bench.jsonl, or to profiles/r09_smoother_bench.jsonl when direct_smooth is among the modes
-(--out).  Timing class 1 and 2 events are only on in the second pass, so steps_per_s is measured without them.  --repeat R measures the
-modes R times in turn (direct, direct_smooth, direct, direct_smooth, ...) and reports each mode's best steps_per_s and lowest solve_ms
-with the list of all of them: the modes alternate inside one process, so that a drift of the machine does not land on one of them.
+and appends them to profiles/r08_direct_bench.jsonl, to profiles/r09_smoother_bench.jsonl when direct_smooth is among the modes, or to
+profiles/r10_cross_bench.jsonl when direct_cross is (--out).  Timing class 1 and 2 events are only on in the second pass, so
+steps_per_s is measured without them.  --repeat R measures the modes R times in turn (direct, direct_smooth, direct_cross, direct,
+direct_smooth, direct_cross, ...) and reports each mode's best steps_per_s and lowest solve_ms with the list of all of them: the modes
+alternate inside one process, so that a drift of the machine does not land on one of them.
     python tools/direct_bench.py [shape ...] [--steps 200] [--modes cold,warm,direct] [--repeat 1] [--out FILE]
-    python tools/direct_bench.py --modes direct,direct_smooth --repeat 3          # the smoother against its yardstick"""
+    python tools/direct_bench.py --modes direct,direct_smooth --repeat 3          # the smoother against its yardstick
+    python tools/direct_bench.py --modes direct,direct_smooth,direct_cross --repeat 3   # the cross-covariances against theirs"""
 import argparse
 import json
 import os
@@ -34,7 +37,7 @@ SHAPES = {
     "go1_foot": (go1_params, 4096, {"leg_odom_type": 1}),
 }
 MODES = {"cold": dict(), "warm": dict(warm_start=True), "direct": dict(solver="direct"),
-         "direct_smooth": dict(solver="direct", smoother=True)}
+         "direct_smooth": dict(solver="direct", smoother=True), "direct_cross": dict(solver="direct", smoother=True, cross=True)}
 
 
 def one(p, B, sd, W, steps, mode):
@@ -82,7 +85,8 @@ def main():
     a = ap.parse_args()
     modes = a.modes.split(",")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "r09_smoother_bench.jsonl" if "direct_smooth" in modes else "r08_direct_bench.jsonl")
+        a.out = os.path.join(ROOT, "profiles", "r10_cross_bench.jsonl" if "direct_cross" in modes else
+                             "r09_smoother_bench.jsonl" if "direct_smooth" in modes else "r08_direct_bench.jsonl")
     for name in a.shapes:
         maker, B, kw = SHAPES[name]
         p = maker()
@@ -108,6 +112,11 @@ def main():
         if "direct" in line and "direct_smooth" in line:
             line["smooth_solve_ms_over_direct"] = line["direct_smooth"]["solve_ms"] / line["direct"]["solve_ms"]
             line["smooth_steps_per_s_over_direct"] = line["direct_smooth"]["steps_per_s"] / line["direct"]["steps_per_s"]
+        if "direct_cross" in line:
+            for m, tag in (("direct", "direct"), ("direct_smooth", "smooth")):
+                if m in line:
+                    line[f"cross_solve_ms_over_{tag}"] = line["direct_cross"]["solve_ms"] / line[m]["solve_ms"]
+                    line[f"cross_steps_per_s_over_{tag}"] = line["direct_cross"]["steps_per_s"] / line[m]["steps_per_s"]
         print(json.dumps(line), flush=True)
         if a.out:
             with open(a.out, "a") as f:
