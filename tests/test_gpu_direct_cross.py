@@ -1,80 +1,20 @@
 """The window cross-covariances of the direct smoother on the GPU (dekf_set_window_cross / dekf_get_window_cross,
 BatchedEstimator(solver="direct", smoother=True, cross=True)): every written block of cov_lag1 and cov_newest of every checked window
-against the matching off-diagonal block of the inverse of the oracle QP's KKT matrix (test_direct_cross.cross_reference), past the
+against the matching off-diagonal block of the inverse of the oracle QP's KKT matrix (direct_lib.cross_reference), past the
 tick where VO rows turn into equalities; the bit identities with the option off and inside the new arrays, batch independence, reset,
 host and device pointers; the call-order contract; an instance poisoned by a NaN sample; the C++ shim."""
 import ctypes as C
-import functools
-import subprocess
 
 import numpy as np
 import pytest
 
-import oracle_lib as O
-from decentralized_ekf_mhe_amd import capi, go1_params, pogox_params
+from decentralized_ekf_mhe_amd import capi, go1_params
 from decentralized_ekf_mhe_amd.estimator import BatchedEstimator, relative_cov, streams_host
-from decentralized_ekf_mhe_amd.streams import make_streams
-from test_direct_cross import build_shim_cross, cross_errors, cross_reference
-from test_direct_smoother import FILL
-from test_direct_solve import CREL, _params, rough_streams
-from test_gpu_direct_solve import sub_streams
+from direct_lib import CROSS_CASES as CASES
+from direct_lib import (CREL, _params, build_shim, case_run, check_reset_rerun, check_window_pointers, cross_errors, cross_reference,
+                        poisoned_runs, rough_streams, run, shim_rows, shim_twin, sub_streams)
 
 pytestmark = pytest.mark.gpu
-
-
-def run_cross(p, s, B, K, every=1, reset_rerun=False, keep=None, cross=True):
-    """x, v_b, status, Cov(x_T), the window and (cross) the cross-covariances (K, x_win, cov_win, lag1, newest of the instances `keep`,
-    default all) of a smoothing handle with or without the option, at the read ticks (every `every`-th tick and the last); the window
-    arrays from tick 1 on"""
-    est = BatchedEstimator(p, B, solver="direct", smoother=True, cross=cross)
-    sh = streams_host(s)
-    keep = list(range(B)) if keep is None else keep
-    res = []
-    lists = ("xw", "cw", "l1", "zn")
-    for _ in range(2 if reset_rerun else 1):
-        out = {k: [] for k in ("x", "vb", "st", "it", "cov", "ticks", "K") + lists}
-        for k in range(K):
-            est.push_stream_step(sh, k)
-            est.step(k)
-            if k % every == 0 or k == K - 1:
-                o, info = est.get(), est.solver_info()
-                out["x"].append(o["x"]); out["vb"].append(o["v_b"]); out["st"].append(o["status"]); out["it"].append(info["iters"])
-                out["ticks"].append(k)
-                if k:
-                    out["cov"].append(est.mhe_cov())
-                    Kw, xw, cw = est.window()
-                    out["K"].append(Kw); out["xw"].append(xw[keep]); out["cw"].append(cw[keep])
-                    if cross:
-                        Kc, l1, zn = est.window_cross()
-                        assert Kc == Kw and l1.shape[1] == Kw - 1 and zn.shape[1] == Kw
-                        out["l1"].append(l1[keep]); out["zn"].append(zn[keep])
-        r = {k: (v if k in lists else np.array(v)) for k, v in out.items()}
-        r["kernel"] = (est.solve_kernel_name(True), est.solve_kernel_name(False))
-        res.append(r)
-        if reset_rerun:
-            est.reset()
-    est.close()
-    return res if reset_rerun else res[0]
-
-
-# name: (params, B, ticks, instances checked, every, kernel).  The smallest shapes that take every path: Go1 is the _4_n20 twin with the
-# fast (even) and the slow (odd) camera; go1_foot has ns = 21, several entries per lane and the blocks that bound LDS; PogoX is the
-# run-time horizon with a 99-step chain of Z.  The foot-state references are KKT systems ~2 200 wide (every 8th tick, which still
-# takes the window fill, full windows and, from tick 40 on, VO equality rows), PogoX's ~3 900 wide (every 10th, one instance).
-CASES = {
-    "go1": (lambda: _params(go1_params), 6, 48, [0, 1], 1, "k_mhe_solve_direct_4_n20"),
-    "go1_foot": (lambda: _params(go1_params, leg_odom_type=1), 4, 48, [0, 1], 8, "k_mhe_solve_direct_foot_4"),
-    "pogox_n100": (lambda: _params(pogox_params), 2, 111, [0], 10, "k_mhe_solve_direct_1"),
-    "go1_foot_info": (lambda: _params(go1_params, leg_odom_type=1, arrival_cost_form=1), 2, 48, [0], 8, "k_mhe_solve_direct_foot_4"),
-}
-
-
-@functools.lru_cache(maxsize=None)
-def cross_case_run(name):
-    mk, B, K, sub, every, kernel = CASES[name]
-    p = mk()
-    s = rough_streams(p, B, K)
-    return p, s, run_cross(p, s, B, K, every=every)
 
 
 def check_identities(r, i):
@@ -87,7 +27,7 @@ def check_identities(r, i):
 # ------------------------------------------------------------------ every cross block, every checked tick
 @pytest.mark.parametrize("name", list(CASES))
 def test_every_cross_block_is_a_block_of_the_kkt_inverse(name):
-    p, s, r = cross_case_run(name)
+    p, s, _, r = case_run(name, "cross")
     _, B, K, sub, every, kernel = CASES[name]
     assert r["kernel"] == (kernel + "_smooth_cross", kernel + "_smooth_cross")
     ticks = [int(k) for k in r["ticks"] if k >= 1]
@@ -124,9 +64,9 @@ def test_every_cross_block_is_a_block_of_the_kkt_inverse(name):
 # ------------------------------------------------------------------ bit identities
 @pytest.mark.parametrize("name", ["go1", "go1_foot", "pogox_n100"])
 def test_cross_on_equals_cross_off_and_the_new_arrays_agree_with_each_other(name):
-    p, s, on = cross_case_run(name)
+    p, s, _, on = case_run(name, "cross")
     _, B, K, _, every, kernel = CASES[name]
-    off = run_cross(p, s, B, K, every=every, cross=False)
+    off = run(p, s, B, K, smoother=True, every=every)
     assert off["kernel"] == (kernel + "_smooth", kernel + "_smooth")
     for key in ("x", "vb", "st", "it", "cov", "ticks", "K"):
         assert np.array_equal(on[key], off[key]), key
@@ -145,8 +85,8 @@ def test_same_cross_bits_at_b6_and_b70():
     p = _params(go1_params)
     B, K = 70, 48
     s = rough_streams(p, B, K)
-    big = run_cross(p, s, B, K, every=3, keep=list(range(6)))
-    small = run_cross(p, sub_streams(s, list(range(6)), B), 6, K, every=3)
+    big = run(p, s, B, K, smoother=True, cross=True, every=3, keep=list(range(6)))
+    small = run(p, sub_streams(s, list(range(6)), B), 6, K, smoother=True, cross=True, every=3)
     for key in ("x", "vb", "st", "cov"):
         assert np.array_equal(small[key], big[key][:, :6]), key
     assert np.array_equal(small["K"], big["K"])
@@ -156,60 +96,11 @@ def test_same_cross_bits_at_b6_and_b70():
 
 
 def test_reset_rerun_reproduces_the_cross_bits():
-    p = _params(go1_params)
-    B, K = 8, 30
-    s = rough_streams(p, B, K)
-    a, b = run_cross(p, s, B, K, every=3, reset_rerun=True)
-    fresh = run_cross(p, s, B, K, every=3)
-    for other in (a, b):
-        for key in ("x", "vb", "st", "cov", "K"):
-            assert np.array_equal(other[key], fresh[key]), key
-        for i in range(len(fresh["K"])):
-            for key in ("xw", "cw", "l1", "zn"):
-                assert np.array_equal(other[key][i], fresh[key][i]), (key, i)
+    check_reset_rerun("cross", ("xw", "cw", "l1", "zn"))
 
 
 def test_host_and_device_pointers_agree_and_entries_past_k_are_untouched():
-    import torch
-    lib = capi.load()
-    p = _params(go1_params)
-    B, ns, N = 5, p.dim_state, p.N
-    s = rough_streams(p, B, N + 4)
-    est = BatchedEstimator(p, B, solver="direct", smoother=True, cross=True)
-    sh = streams_host(s)
-    for k in range(N + 4):
-        est.push_stream_step(sh, k)
-        est.step(k)
-        if k not in (1, 7, N - 2, N - 1, N + 3):
-            continue
-        Kw = min(k + 1, N)
-        lh, zh = np.full((B, N - 1, ns, ns), FILL), np.full((B, N, ns, ns), FILL)
-        kh = C.c_int(0)
-        assert lib.dekf_get_window_cross(est.h, C.byref(kh), lh.ctypes.data, zh.ctypes.data, capi.DEKF_HOST) == capi.DEKF_OK
-        assert kh.value == Kw
-        assert (lh[:, Kw - 1:] == FILL).all() and (zh[:, Kw:] == FILL).all(), k
-        assert np.isfinite(lh[:, :Kw - 1]).all() and np.isfinite(zh[:, :Kw]).all(), k
-        ld = torch.full((B, N - 1, ns, ns), FILL, dtype=torch.float64, device="cuda")
-        zd = torch.full((B, N, ns, ns), FILL, dtype=torch.float64, device="cuda")
-        torch.cuda.synchronize()
-        kd = C.c_int(0)
-        assert lib.dekf_get_window_cross(est.h, C.byref(kd), ld.data_ptr(), zd.data_ptr(), capi.DEKF_DEVICE) == capi.DEKF_OK
-        est.sync()
-        assert kd.value == Kw
-        assert np.array_equal(ld.cpu().numpy(), lh) and np.array_equal(zd.cpu().numpy(), zh), k
-        # any of the three pointers may be NULL
-        l2 = np.full((B, N - 1, ns, ns), FILL)
-        assert lib.dekf_get_window_cross(est.h, None, l2.ctypes.data, None, capi.DEKF_HOST) == capi.DEKF_OK
-        assert np.array_equal(l2, lh)
-        z2 = np.full((B, N, ns, ns), FILL)
-        assert lib.dekf_get_window_cross(est.h, None, None, z2.ctypes.data, capi.DEKF_HOST) == capi.DEKF_OK
-        assert np.array_equal(z2, zh)
-        k3 = C.c_int(0)
-        assert lib.dekf_get_window_cross(est.h, C.byref(k3), None, None, capi.DEKF_HOST) == capi.DEKF_OK and k3.value == Kw
-        # window_cross() hands out the written entries
-        Kp, lp, zp = est.window_cross()
-        assert Kp == Kw and np.array_equal(lp, lh[:, :Kw - 1]) and np.array_equal(zp, zh[:, :Kw])
-    est.close()
+    check_window_pointers(cross=True)
 
 
 # ------------------------------------------------------------------ contract
@@ -296,71 +187,26 @@ def test_kernel_name_names_the_cross_twin():
 
 # ------------------------------------------------------------------ a NaN sample
 def test_nan_sample_poisons_only_its_own_cross_arrays():
-    p = _params(go1_params)
-    B, K, bad, t_bad = 6, 34, 2, 26
-    s = rough_streams(p, B, K)
-    clean = run_cross(p, s, B, K)
-    sp = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in s.items()}
-    sp["accel"][t_bad, bad, 0] = np.nan      # (the smoother test's input: poisoned data, no fault)
-    pois = run_cross(p, sp, B, K)
-    others = [b for b in range(B) if b != bad]
-    for key in ("x", "vb", "st", "cov"):
-        assert np.array_equal(pois[key][:, others], clean[key][:, others]), key
-    assert np.array_equal(pois["K"], clean["K"])
-    assert (clean["st"][1:] == capi.DEKF_SOLVE_OK).all()
-    assert pois["st"][t_bad, bad] == capi.DEKF_SOLVE_NUMERIC
-    n_numeric = 0
-    for i in range(len(clean["K"])):
-        for key in ("l1", "zn"):
-            assert np.array_equal(pois[key][i][others], clean[key][i][others]), (key, i)
-            assert np.isfinite(clean[key][i]).all(), (key, i)
-        if pois["st"][i + 1, bad] == capi.DEKF_SOLVE_NUMERIC:     # (read tick i + 1: the window arrays start at tick 1)
-            n_numeric += 1
-            assert np.isnan(pois["l1"][i][bad]).all() and np.isnan(pois["zn"][i][bad]).all(), i
-    assert n_numeric >= 1
+    poisoned_runs("cross", ("l1", "zn"))
 
 
 # ------------------------------------------------------------------ the C++ shim
 def test_shim_cross_arrays_equal_batched_estimator(tmp_path):
-    exe = build_shim_cross(tmp_path)
     p = _params(go1_params)
     K = 30
-    s = make_streams(p, 1, K)
-    quats = O.run_streams(p, s)[2][:, 0]
-    log = np.zeros((K, 81))
-    for k in range(K):
-        log[k, 0] = s["imu_t"][k, 0]
-        log[k, 1:4], log[k, 4:7], log[k, 7:11] = s["accel"][k, 0], s["gyro"][k, 0], quats[k]
-        log[k, 11:23] = s["p_foot"][k, 0].ravel()
-        log[k, 23:59] = s["J"][k, 0].ravel()
-        log[k, 59:71] = s["qdot"][k, 0].ravel()
-        log[k, 71:75] = s["contact"][k, 0]
-        if s["vo_mask"][k, 0]:
-            log[k, 75], log[k, 76], log[k, 77], log[k, 78:81] = 1.0, s["vo_t_pre"][k, 0], s["vo_t_now"][k, 0], s["vo_dp"][k, 0]
-    path = tmp_path / "log.bin"
-    log.tofile(path)
-    r = subprocess.run([exe, str(path), str(K)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    rows = [[float(v) for v in line.split()[1:]] for line in r.stdout.strip().splitlines()]
-    est = BatchedEstimator(p, 1, solver="direct", smoother=True, cross=True)
-    sh = streams_host(s)
-    for k in range(K):
-        est.push_stream_step(sh, k)
-        est.push_quaternion(np.ascontiguousarray(quats[k][None, :]))
-        est.update(k) if k else est.initialize()
-        if k:
-            row = np.array(rows[k])
-            Kw, xw, cw = est.window()
-            Kc, l1, zn = est.window_cross()
-            assert np.array_equal(row[0:9], est.get()["x"][0]), k        # (the shim prints %.17g: a double round-trips exactly)
-            assert int(row[12]) == Kw == Kc == min(k + 1, p.N), k
-            o = 13
-            for j in range(Kw):
-                assert np.array_equal(row[o:o + 81].reshape(9, 9), cw[0, j]), (k, j)
-                assert np.array_equal(row[o + 81:o + 162].reshape(9, 9), zn[0, j]), (k, j)
-                o += 162
-                if j + 1 < Kw:
-                    assert np.array_equal(row[o:o + 81].reshape(9, 9), l1[0, j]), (k, j)
-                    o += 81
-            assert o + 1 == len(row), k                                   # (solver_iters_ closes the line)
-    est.close()
+    s, quats, rows = shim_rows(build_shim(tmp_path, "cross"), tmp_path, p, K)
+    for k, est in shim_twin(p, s, quats, K, "cross"):
+        row = rows[k]
+        Kw, xw, cw = est.window()
+        Kc, l1, zn = est.window_cross()
+        assert np.array_equal(row[0:9], est.get()["x"][0]), k        # (the shim prints %.17g: a double round-trips exactly)
+        assert int(row[12]) == Kw == Kc == min(k + 1, p.N), k
+        o = 13
+        for j in range(Kw):
+            assert np.array_equal(row[o:o + 81].reshape(9, 9), cw[0, j]), (k, j)
+            assert np.array_equal(row[o + 81:o + 162].reshape(9, 9), zn[0, j]), (k, j)
+            o += 162
+            if j + 1 < Kw:
+                assert np.array_equal(row[o:o + 81].reshape(9, 9), l1[0, j]), (k, j)
+                o += 81
+        assert o + 1 == len(row), k                                   # (solver_iters_ closes the line)

@@ -1,79 +1,25 @@
 """The direct MHE solve on the GPU (dekf_set_solver(h, DEKF_SOLVER_DIRECT), BatchedEstimator(solver="direct")): every checked tick
-against the exact optimum of the oracle's QP and the covariance against the inverse of its KKT matrix (test_direct_solve.py's
-references), past the tick where VO rows turn into equalities, the Kalman-filter identity without VO, the distance of the cold ADMM oracle from the optimum (a record), batch
+against the exact optimum of the oracle's QP and the covariance against the inverse of its KKT matrix (direct_lib.exact_reference),
+past the tick where VO rows turn into equalities, the Kalman-filter identity without VO, the distance of the cold ADMM oracle from the optimum (a record), batch
 independence, defaults and reset, the call-order contract, an instance poisoned by a NaN sample, the C++ shim and the kernel name."""
-import functools
-import subprocess
-
 import numpy as np
 import pytest
 
 import oracle_lib as O
 import ref_numpy as RN
-from decentralized_ekf_mhe_amd import capi, cassie_params, go1_params, pogox_params
+from decentralized_ekf_mhe_amd import capi, cassie_params, go1_params
 from decentralized_ekf_mhe_amd.estimator import BatchedEstimator, streams_host
 from decentralized_ekf_mhe_amd.streams import make_streams
-from test_direct_solve import (CREL, XABS, XREL, _params, block_err, blocks3, build_shim_direct, cov_err, exact_reference,
-                               rough_streams, tripod_params)
+from direct_lib import (CASES, CREL, XABS, XREL, _params, block_err, blocks3, build_shim, case_run, check_reset_rerun, cov_err,
+                        exact_reference, poisoned_runs, rough_streams, run, shim_rows, shim_twin, sub_streams, tripod_params)
 
 pytestmark = pytest.mark.gpu
-
-
-def run(p, s, B, K, solver="direct", every=1, reset_rerun=False):
-    """x, v_b, status, iters, residuals and (direct) Cov(x_T) at the read ticks (every `every`-th tick and the last)"""
-    est = BatchedEstimator(p, B, solver=solver)
-    sh = streams_host(s)
-    res = []
-    for _ in range(2 if reset_rerun else 1):
-        out = {k: [] for k in ("x", "vb", "st", "it", "pri", "cov", "ticks")}
-        for k in range(K):
-            est.push_stream_step(sh, k)
-            est.step(k)
-            if k % every == 0 or k == K - 1:
-                o, info = est.get(), est.solver_info()
-                out["x"].append(o["x"]); out["vb"].append(o["v_b"]); out["st"].append(o["status"]); out["it"].append(info["iters"])
-                out["pri"].append(info["pri_res"]); out["ticks"].append(k)
-                if solver == "direct" and k:
-                    out["cov"].append(est.mhe_cov())
-        r = {k: np.array(v) for k, v in out.items()}
-        r["kernel"] = (est.solve_kernel_name(True), est.solve_kernel_name(False))
-        res.append(r)
-        if reset_rerun:
-            est.reset()
-    est.close()
-    return res if reset_rerun else res[0]
-
-
-def sub_streams(s, idx, B):
-    so = {k: (np.ascontiguousarray(v[:, idx]) if isinstance(v, np.ndarray) and v.ndim >= 2 and v.shape[1] == B else v) for k, v in s.items()}
-    so["vo_any"] = so["vo_mask"].any(axis=1)
-    return so
-
-
-# name: (params, B, K, oracle instances, every, direct kernel).  rough_streams: the even instances carry the 30 Hz camera, whose VO rows
-# turn into equalities from tick 40 on (the odd ones the slow camera): every case runs past that and checks even and odd instances.
-CASES = {
-    "go1_832": (lambda: _params(go1_params), 832, 48, [0, 1, 416, 831], 1, "k_mhe_solve_direct_4_n20"),
-    "cassie": (lambda: _params(cassie_params), 6, 48, [0, 3], 1, "k_mhe_solve_direct_2_n20"),
-    "pogox_n100": (lambda: _params(pogox_params), 4, 111, [0, 1], 10, "k_mhe_solve_direct_1"),  # (KKT systems ~3 900 wide: every 10th tick)
-    "tripod": (lambda: tripod_params(), 6, 48, [0, 5], 1, "k_mhe_solve_direct_3"),
-    "go1_foot": (lambda: _params(go1_params, leg_odom_type=1), 6, 48, [0, 1], 1, "k_mhe_solve_direct_foot_4"),
-    "go1_foot_info": (lambda: _params(go1_params, leg_odom_type=1, arrival_cost_form=1), 4, 48, [2], 1, "k_mhe_solve_direct_foot_4"),
-}
-
-
-@functools.lru_cache(maxsize=None)
-def case_run(name):
-    mk, B, K, sub, every, kernel = CASES[name]
-    p = mk()
-    s = rough_streams(p, B, K)
-    return p, s, run(p, s, B, K, every=every)
 
 
 # ------------------------------------------------------------------ 3: exactness, every checked tick
 @pytest.mark.parametrize("name", list(CASES))
 def test_direct_is_the_exact_optimum_of_the_oracle_qp(name):
-    p, s, r = case_run(name)
+    p, s, _, r = case_run(name, "plain")
     _, B, K, sub, every, kernel = CASES[name]
     assert r["kernel"] == (kernel, kernel)
     ticks = [int(k) for k in r["ticks"] if k >= 1]
@@ -166,7 +112,7 @@ def test_direct_against_the_cold_admm_oracle(name):
 
 # ------------------------------------------------------------------ 5: batch independence
 def test_same_bits_at_b6_and_b832():
-    p, s, big = case_run("go1_832")
+    p, s, _, big = case_run("go1_832", "plain")
     _, B, K, _, every, _ = CASES["go1_832"]
     small = run(p, sub_streams(s, list(range(6)), B), 6, K, every=every)
     for key in ("x", "vb", "st", "cov"):
@@ -194,14 +140,7 @@ def test_explicit_admm_equals_default_handle():
 
 
 def test_reset_rerun_equals_fresh_direct_handle():
-    p = _params(go1_params)
-    B, K = 8, 30
-    s = rough_streams(p, B, K)
-    a, b = run(p, s, B, K, every=3, reset_rerun=True)
-    fresh = run(p, s, B, K, every=3)
-    for key in ("x", "vb", "st", "cov"):
-        assert np.array_equal(a[key], fresh[key]), key
-        assert np.array_equal(b[key], fresh[key]), key
+    check_reset_rerun("plain")
 
 
 # ------------------------------------------------------------------ 7: contract
@@ -250,55 +189,19 @@ def test_call_order_and_refusals():
 
 
 def test_nan_sample_poisons_only_its_own_instance():
-    p = _params(go1_params)
-    B, K, bad, t_bad = 6, 34, 2, 26
-    s = rough_streams(p, B, K)
-    clean = run(p, s, B, K)
-    sp = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in s.items()}
-    sp["accel"][t_bad, bad, 0] = np.nan
-    pois = run(p, sp, B, K)
-    others = [b for b in range(B) if b != bad]
-    for key in ("x", "vb", "st", "cov"):
-        assert np.array_equal(pois[key][:, others], clean[key][:, others]), key
-    assert pois["st"][t_bad, bad] == capi.DEKF_SOLVE_NUMERIC
-    assert (clean["st"][1:] == capi.DEKF_SOLVE_OK).all()
+    poisoned_runs("plain")
 
 
 # ------------------------------------------------------------------ 8: the C++ shim
 def test_shim_direct_equals_batched_estimator(tmp_path):
-    exe = build_shim_direct(tmp_path)
     p = _params(go1_params)
     K = 40
-    s = make_streams(p, 1, K)
-    quats = O.run_streams(p, s)[2][:, 0]
-    log = np.zeros((K, 81))
-    for k in range(K):
-        log[k, 0] = s["imu_t"][k, 0]
-        log[k, 1:4], log[k, 4:7], log[k, 7:11] = s["accel"][k, 0], s["gyro"][k, 0], quats[k]
-        log[k, 11:23] = s["p_foot"][k, 0].ravel()
-        log[k, 23:59] = s["J"][k, 0].ravel()
-        log[k, 59:71] = s["qdot"][k, 0].ravel()
-        log[k, 71:75] = s["contact"][k, 0]
-        if s["vo_mask"][k, 0]:
-            log[k, 75], log[k, 76], log[k, 77], log[k, 78:81] = 1.0, s["vo_t_pre"][k, 0], s["vo_t_now"][k, 0], s["vo_dp"][k, 0]
-    path = tmp_path / "log.bin"
-    log.tofile(path)
-    r = subprocess.run([exe, str(path), str(K)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    rows = np.array([[float(v) for v in line.split()[1:]] for line in r.stdout.strip().splitlines()])
-    # the same robot through BatchedEstimator(solver="direct"), with the orientation the shim was given
-    est = BatchedEstimator(p, 1, solver="direct")
-    sh = streams_host(s)
-    for k in range(K):
-        est.push_stream_step(sh, k)
-        est.push_quaternion(np.ascontiguousarray(quats[k][None, :]))
-        est.update(k) if k else est.initialize()
-        if k:
-            o = est.get()
-            assert np.array_equal(rows[k, 0:9], o["x"][0]), k        # (the shim prints %.17g: a double round-trips exactly)
-            assert np.array_equal(rows[k, 9:12], o["v_b"][0]), k
-            assert np.array_equal(rows[k, 12:93].reshape(9, 9), est.mhe_cov()[0]), k
-    est.close()
+    s, quats, rows = shim_rows(build_shim(tmp_path, "plain"), tmp_path, p, K)
+    for k, est in shim_twin(p, s, quats, K, "plain"):
+        o = est.get()
+        assert np.array_equal(rows[k][0:9], o["x"][0]), k        # (the shim prints %.17g: a double round-trips exactly)
+        assert np.array_equal(rows[k][9:12], o["v_b"][0]), k
+        assert np.array_equal(rows[k][12:93].reshape(9, 9), est.mhe_cov()[0]), k
 
 
 # ------------------------------------------------------------------ 9: kernel name

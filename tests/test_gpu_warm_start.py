@@ -11,25 +11,10 @@ import oracle_lib as O
 import ref_numpy as RN
 from decentralized_ekf_mhe_amd import capi, cassie_params, go1_params, pogox_params
 from decentralized_ekf_mhe_amd.estimator import BatchedEstimator, streams_host
-from decentralized_ekf_mhe_amd.streams import make_streams
+from direct_lib import _params, rough_streams, tripod_params
 
 pytestmark = pytest.mark.gpu
 RTOL, ATOL = 1e-4, 1e-6
-
-
-def _params(maker, **kw):
-    p = maker()
-    p.ekf_rate = p.rate
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def tripod_params(**kw):
-    """3 legs x 6 joints at N = 12: no fixed-horizon kernel, the generic family solves every tick"""
-    p = _params(go1_params, N=12, **kw)
-    p.num_legs, p.joints_per_leg = 3, 6
-    return p
 
 
 def block_err(x, ref, blocks):
@@ -47,24 +32,6 @@ def base_blocks():
 
 def foot_blocks(L):
     return [slice(9 + 3 * i, 12 + 3 * i) for i in range(L)]
-
-
-def rough_streams(p, B, K, seed_shift=0):
-    """make_streams logs with VO, camera drop-outs, a slow late camera on half the fleet and a flight phase longer than the window"""
-    s = make_streams(p, B, K, first_instance=seed_shift, vo_rate=30.0)
-    slow = make_streams(p, B, K, first_instance=seed_shift, vo_rate=3.75, vo_latency=0.06)
-    half = np.arange(B) % 2 == 1
-    for key in ("vo_mask", "vo_t_pre", "vo_t_now", "vo_dp", "vo_t_pose", "vo_q"):
-        s[key][:, half] = slow[key][:, half]
-    s["vo_any"] = s["vo_mask"].any(axis=1)
-    L = p.num_legs
-    f0, f1 = min(22, K - 1), min(22 + p.N + 4, K)
-    s["contact"][f0:f1, ::3] = 0.0                        # every third robot in flight for longer than the window
-    d0, d1 = min(30, K - 1), min(45, K)
-    s["vo_mask"][d0:d1, 1::4] = 0                         # a camera drop-out on every fourth robot
-    s["vo_any"] = s["vo_mask"].any(axis=1)
-    assert s["contact"].shape[-1] == L
-    return s
 
 
 def run(p, s, B, K, warm, every=1, reset_rerun=False, on_step=None):
