@@ -14,6 +14,7 @@
 #include "kf_core.h"
 #include "mhe_assemble_core.h"
 #include "mhe_direct_core.h"
+#include "mhe_epoch_core.h"
 #include "mhe_solve_core.h"
 
 using namespace dekf;
@@ -34,7 +35,10 @@ __global__ void k_mhe_marginalize_early(DevCfg c, DevState s, int T);
 #define DEKF_DIRECT_KERNEL(NAME, ...)                                               \
     __global__ void NAME(DevCfg c, DevState s, int kstart, int K, double* cov);   \
     __global__ void NAME##_smooth(DevCfg c, DevState s, int kstart, int K, double* cov, DirectWindow win); \
-    __global__ void NAME##_smooth_cross(DevCfg c, DevState s, int kstart, int K, double* cov, DirectWindow win, DirectCross cross);
+    __global__ void NAME##_smooth_cross(DevCfg c, DevState s, int kstart, int K, double* cov, DirectWindow win, DirectCross cross); \
+    __global__ void NAME##_ep(DevCfg c, DevState s, int T, double* cov, const int* t0); \
+    __global__ void NAME##_smooth_ep(DevCfg c, DevState s, int T, double* cov, DirectWindow win, const int* t0); \
+    __global__ void NAME##_smooth_cross_ep(DevCfg c, DevState s, int T, double* cov, DirectWindow win, DirectCross cross, const int* t0);
 #include "direct_kernels.def"
 __global__ void k_gap();
 __global__ void k_kf_initialize(DevCfg c, DevState s);
@@ -42,6 +46,12 @@ __global__ void k_kf_update(DevCfg c, DevState s, int pushes);
 __global__ void k_latch_vo(DevCfg c, DevState s, const int* mask, const double* t_pre, const double* t_now,
                            const double* dp, const double* t_pose, const double* q_vo);
 __global__ void k_reset_state(DevCfg c, DevState s);
+// restarting single instances (mhe_epoch_core.h)
+__global__ void k_reset_instances(DevCfg c, DevState s, const int* mask, double* cov, int* t0, int* c0, int next_T, int ekf_count);
+__global__ void k_fold_epochs(int* c0, int B, int count_old, int count_new, int H);
+__global__ void k_ekf_tick_ep(DevCfg c, DevState s, int count, const int* c0);
+__global__ void k_mhe_assemble_ep(DevCfg c, DevState s, int T, int pushes, const int* t0);
+__global__ void k_mhe_marginalize_early_ep(DevCfg c, DevState s, int T, const int* t0);
 __global__ void k_ekf_cov_out(DevCfg c, DevState s, double* out);
 __global__ void k_latch4(LatchCopy4 a);
 __global__ void k_go1_leg_odometry(DevCfg c, DevState s, const double* jp, const double* jv, const double* force,
@@ -93,6 +103,14 @@ struct dekf_handle_s {
     // win.t1's entries into Cov(x_k, x_{k+1}) and leaves Cov(x_k, x_T) in cross_st.newest (mhe_direct_core.h: DirectCross)
     bool cross = false;
     DirectCross cross_st;
+    // dekf_reset_instances: the epochs of a direct handle (mhe_epoch_core.h).  ep_t0 | ep_c0: [B] ints each on the device, the handle's
+    // step and EKF tick count at every instance's last restart (0: never), allocated by the first call with a non-zero mask; t0_host:
+    // the host's copy of ep_t0 (dekf_get_instance_ticks, the window getters' steps), min_t0 its smallest entry.  epochs: a non-zero
+    // mask has been applied since dekf_create / dekf_reset — the handle launches the *_ep kernels, which take the two arrays
+    int *ep_t0 = nullptr, *ep_c0 = nullptr;
+    std::vector<int> t0_host;
+    int min_t0 = 0;
+    bool epochs = false;
     size_t lds_solve = 0, lds_asm = 0, lds_kf = 0;
     int ekf_count = 0, pushes = 0, next_T = 0;
     bool initialized = false;
@@ -186,6 +204,9 @@ const SolveKernel* solve_kernel(SolveRole role, int L, int N) {
 typedef void (*DirectFn)(DevCfg, DevState, int, int, double*);
 typedef void (*DirectSmoothFn)(DevCfg, DevState, int, int, double*, DirectWindow);
 typedef void (*DirectCrossFn)(DevCfg, DevState, int, int, double*, DirectWindow, DirectCross);
+typedef void (*DirectEpochFn)(DevCfg, DevState, int, double*, const int*);
+typedef void (*DirectSmoothEpochFn)(DevCfg, DevState, int, double*, DirectWindow, const int*);
+typedef void (*DirectCrossEpochFn)(DevCfg, DevState, int, double*, DirectWindow, DirectCross, const int*);
 struct DirectKernel {
     int legs, ft, nfix;  // direct_solve_t's L and FT; the horizon the row is meant for (0: any)
     DirectFn fn;
@@ -194,9 +215,15 @@ struct DirectKernel {
     const char* name_smooth;
     DirectCrossFn fn_cross;  // the twin with the window cross-covariances (dekf_set_window_cross)
     const char* name_cross;
+    // the epoch twins of the three (dekf_reset_instances)
+    DirectEpochFn fn_ep;
+    DirectSmoothEpochFn fn_smooth_ep;
+    DirectCrossEpochFn fn_cross_ep;
+    const char *name_ep, *name_smooth_ep, *name_cross_ep;
 };
-#define DEKF_DIRECT_KERNEL(NAME, L, FT, NFIX) \
-    {L, FT, NFIX, NAME, #NAME, NAME##_smooth, #NAME "_smooth", NAME##_smooth_cross, #NAME "_smooth_cross"},
+#define DEKF_DIRECT_KERNEL(NAME, L, FT, NFIX)                                                                          \
+    {L, FT, NFIX, NAME, #NAME, NAME##_smooth, #NAME "_smooth", NAME##_smooth_cross, #NAME "_smooth_cross",             \
+     NAME##_ep, NAME##_smooth_ep, NAME##_smooth_cross_ep, #NAME "_ep", #NAME "_smooth_ep", #NAME "_smooth_cross_ep"},
 const DirectKernel direct_kernels[] = {
 #include "direct_kernels.def"
 };
@@ -563,6 +590,88 @@ dekf_status dekf_reset(dekf_handle h) {
     h->initialized = false;
     h->mhe_cov_valid = false;  // (the solver, smoother and cross settings survive)
     h->win_steps = 0;
+    if (h->ep_t0) {  // every epoch: the handle launches the kernels of a handle that never restarted an instance again
+        HIPCHK(hipMemsetAsync(h->ep_t0, 0, 2 * (size_t)h->c.B * sizeof(int), h->stream));
+        h->t0_host.assign((size_t)h->c.B, 0);
+        h->min_t0 = 0;
+        h->epochs = false;
+    }
+    return DEKF_OK;
+}
+
+dekf_status dekf_reset_instances(dekf_handle h, const int* mask, dekf_mem where) {
+    if (!h) return fail(DEKF_ERR_INVALID, "null handle");
+    if (!mask) return fail(DEKF_ERR_INVALID, "null mask");
+    if (h->c.est_type != 0) return fail(DEKF_ERR_INVALID, "dekf_reset_instances needs a direct MHE handle: this is a KF handle (est_type 1)");
+    if (h->pipelined) return fail(DEKF_ERR_INVALID, "dekf_reset_instances cannot be combined with solve_pipeline = 1");
+    if (h->solver != DEKF_SOLVER_DIRECT) return fail(DEKF_ERR_INVALID, "dekf_reset_instances needs a direct handle (dekf_set_solver(h, DEKF_SOLVER_DIRECT))");
+    if (!h->initialized) return fail(DEKF_ERR_ORDER, "dekf_reset_instances before dekf_initialize");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t B = (size_t)h->c.B;
+    // the host reads the mask: it refuses values other than 0 and 1, and it keeps its own copy of the epochs (a device mask costs a
+    // copy and a wait here; restarts are rare, and the call between two ticks is not on the hot path)
+    std::vector<int> m(B);
+    if (where == DEKF_HOST) std::memcpy(m.data(), mask, B * sizeof(int));
+    else {
+        HIPCHK(hipMemcpyAsync(m.data(), mask, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    bool any = false;
+    for (size_t b = 0; b < B; ++b) {
+        if (m[b] != 0 && m[b] != 1) return fail(DEKF_ERR_INVALID, "dekf_reset_instances: mask entries must be 0 or 1");
+        any = any || m[b] == 1;
+    }
+    if (!any) return DEKF_OK;  // nothing changes, the kernels the handle launches included
+    // what dekf_reset waits for: a solve in flight writes the outputs this clears, the early marginalisation the tags, and an
+    // all-gather's snapshot copy may still be reading v_b
+    for (int i = 0; i < 2; ++i)
+        if (h->solve_pending[i]) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_solve[i], 0)); h->solve_pending[i] = false; }
+    if (h->early_pending) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_early_done, 0)); h->early_pending = false; }
+    for (int i = 0; i < 2; ++i)
+        if (h->vb_read_pending[i]) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_vb_read[i], 0)); h->vb_read_pending[i] = false; }
+    if (!h->ep_t0) {
+        int* e = nullptr;  // t0 | c0 in one block
+        HIPCHK(hipMalloc(&e, 2 * B * sizeof(int)));
+        h->blocks.push_back(e);
+        HIPCHK(hipMemsetAsync(e, 0, 2 * B * sizeof(int), h->stream));
+        h->ep_t0 = e;
+        h->ep_c0 = e + B;
+        h->t0_host.assign(B, 0);
+        h->min_t0 = 0;
+    }
+    const int* dmask = mask;
+    if (where == DEKF_HOST) {
+        dekf_status st = ensure_stage(h, B * sizeof(int));
+        if (st) return st;
+        HIPCHK(hipMemcpyAsync(h->stage, m.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        dmask = (const int*)h->stage;
+    }
+    k_reset_instances<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->s, dmask, h->mhe_cov, h->ep_t0, h->ep_c0, h->next_T, h->ekf_count);
+    HIPCHK(hipGetLastError());
+    if (where == DEKF_HOST) HIPCHK(hipStreamSynchronize(h->stream));  // (m, a local, is the source of the copy)
+    h->min_t0 = h->next_T;
+    for (size_t b = 0; b < B; ++b) {
+        if (m[b]) h->t0_host[b] = h->next_T;
+        if (h->t0_host[b] < h->min_t0) h->min_t0 = h->t0_host[b];
+    }
+    h->epochs = true;
+    return DEKF_OK;
+}
+
+dekf_status dekf_get_instance_ticks(dekf_handle h, int* ticks, dekf_mem where) {
+    if (!h || !ticks) return fail(DEKF_ERR_INVALID, "null argument");
+    if (!h->initialized) return fail(DEKF_ERR_ORDER, "dekf_get_instance_ticks before dekf_initialize");
+    const size_t B = (size_t)h->c.B;
+    const int T = h->next_T - 1;  // the step of the last update (0: dekf_initialize)
+    std::vector<int> t(B, T);
+    if (h->epochs)
+        for (size_t b = 0; b < B; ++b) t[b] = T - h->t0_host[b];
+    if (where == DEKF_HOST) std::memcpy(ticks, t.data(), B * sizeof(int));
+    else {
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipMemcpyAsync(ticks, t.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));  // (t is a local)
+    }
     return DEKF_OK;
 }
 
@@ -658,13 +767,23 @@ dekf_status dekf_ekf_step(dekf_handle h) {
     if (!h) return fail(DEKF_ERR_INVALID, "null handle");
     {
         Timed t(h, 0);
-        k_ekf_tick<<<(h->c.B + 63) / 64, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count);
+        if (h->epochs) k_ekf_tick_ep<<<(h->c.B + 63) / 64, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count, h->ep_c0);
+        else k_ekf_tick<<<(h->c.B + 63) / 64, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count);
     }
     HIPCHK(hipGetLastError());
     h->ekf_count++;
     // the kernel uses the count only modulo the ring depth and to know whether the ring is full: folded long before
     // the int overflows (a 500 Hz node reaches 2^31 ticks after 49 days)
-    if (h->ekf_count >= (1 << 30)) h->ekf_count = h->c.ekf_hist + h->ekf_count % h->c.ekf_hist;
+    if (h->ekf_count >= (1 << 30)) {
+        const int folded = h->c.ekf_hist + h->ekf_count % h->c.ekf_hist;
+        // A restarted instance's tick runs on its local count, ekf_count - c0[b]: every epoch is moved so that the local count keeps
+        // its value modulo the ring depth and whether it has reached it (mhe_epoch_core.h: fold_epoch).  An epoch of 0 stays 0.
+        if (h->epochs) {
+            k_fold_epochs<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->ep_c0, h->c.B, h->ekf_count, folded, h->c.ekf_hist);
+            HIPCHK(hipGetLastError());
+        }
+        h->ekf_count = folded;
+    }
     return DEKF_OK;
 }
 
@@ -707,7 +826,8 @@ dekf_status dekf_update(dekf_handle h, int T) {
         if (h->early_pending) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_early_done, 0)); h->early_pending = false; }
         {
             Timed t(h, 1);
-            k_mhe_assemble<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->c, sp, T, h->pushes);
+            if (h->epochs) k_mhe_assemble_ep<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->c, sp, T, h->pushes, h->ep_t0);
+            else k_mhe_assemble<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->c, sp, T, h->pushes);
         }
         HIPCHK(hipGetLastError());
         if (h->early_stream) HIPCHK(hipEventRecord(h->ev_asm_done, h->stream));
@@ -730,7 +850,14 @@ dekf_status dekf_update(dekf_handle h, int T) {
             { static const int gap = getenv("DEKF_DEBUG_GAP_KERNEL") ? atoi(getenv("DEKF_DEBUG_GAP_KERNEL")) : 0;
               for (int i = 0; i < gap; ++i) k_gap<<<1, 64, 0, ss>>>(); }
 #endif
-            if (h->solver == DEKF_SOLVER_DIRECT && h->smoother && h->cross)
+            // (a direct handle that has restarted an instance: the epoch twins, which find every instance's window from the step)
+            if (h->epochs && h->smoother && h->cross)
+                h->direct->fn_cross_ep<<<h->c.B, 64, h->lds_direct, ss>>>(h->c, sp, T, h->mhe_cov, h->win, h->cross_st, h->ep_t0);
+            else if (h->epochs && h->smoother)
+                h->direct->fn_smooth_ep<<<h->c.B, 64, h->lds_direct, ss>>>(h->c, sp, T, h->mhe_cov, h->win, h->ep_t0);
+            else if (h->epochs)
+                h->direct->fn_ep<<<h->c.B, 64, h->lds_direct, ss>>>(h->c, sp, T, h->mhe_cov, h->ep_t0);
+            else if (h->solver == DEKF_SOLVER_DIRECT && h->smoother && h->cross)
                 h->direct->fn_cross<<<h->c.B, 64, h->lds_direct, ss>>>(h->c, sp, kstart, K, h->mhe_cov, h->win, h->cross_st);
             else if (h->solver == DEKF_SOLVER_DIRECT && h->smoother)
                 h->direct->fn_smooth<<<h->c.B, 64, h->lds_direct, ss>>>(h->c, sp, kstart, K, h->mhe_cov, h->win);
@@ -750,11 +877,16 @@ dekf_status dekf_update(dekf_handle h, int T) {
         h->last_par = par;
         h->mhe_cov_valid = h->solver == DEKF_SOLVER_DIRECT;
         h->win_steps = h->smoother ? T - kstart + 1 : 0;
+        if (h->epochs && h->smoother) {  // the largest window of the batch: the instance restarted longest ago (none at its local step 0)
+            const int Tl = T - h->min_t0;
+            h->win_steps = Tl < 1 ? 0 : (Tl + 1 < h->c.N ? Tl + 1 : h->c.N);
+        }
         if (h->early_stream) {
             // behind the assemble of this step (the arrival cost and the records as it left them), beside this step's solve
             HIPCHK(hipStreamWaitEvent(h->early_stream, h->ev_asm_done, 0));
             HIPCHK(hipEventRecord(h->ev_early_mark, h->early_stream));  // (as before a pipelined solve launch: see there)
-            k_mhe_marginalize_early<<<h->c.B, 64, h->lds_asm, h->early_stream>>>(h->c, h->s, T + 1);
+            if (h->epochs) k_mhe_marginalize_early_ep<<<h->c.B, 64, h->lds_asm, h->early_stream>>>(h->c, h->s, T + 1, h->ep_t0);
+            else k_mhe_marginalize_early<<<h->c.B, 64, h->lds_asm, h->early_stream>>>(h->c, h->s, T + 1);
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(h->ev_early_done, h->early_stream));
             h->early_pending = true;
@@ -1061,6 +1193,7 @@ dekf_status dekf_launch_info(dekf_handle h, int* solve_workgroups, int* compute_
 
 const char* dekf_solve_kernel_name(dekf_handle h, int full_window) {
     if (!h || h->c.est_type != 0) return nullptr;
+    if (h->solver == DEKF_SOLVER_DIRECT && h->epochs) return h->cross ? h->direct->name_cross_ep : h->smoother ? h->direct->name_smooth_ep : h->direct->name_ep;
     if (h->solver == DEKF_SOLVER_DIRECT) return h->cross ? h->direct->name_cross : h->smoother ? h->direct->name_smooth : h->direct->name;
     return (full_window && h->solve_kernel_full) ? h->solve_name_full : h->solve_name;
 }

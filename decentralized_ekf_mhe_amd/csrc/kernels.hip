@@ -10,6 +10,7 @@
 //   k_kf_*            KF alternative                      (kf_core.h)
 //   k_latch_vo        masked VO latch (robotSub::vo_callback for a batch)
 //   k_latch4          device-to-device sensor latch of one push (IMU or leg arrays) in one launch
+//   k_reset_instances, k_*_ep   restarting single instances of a direct handle (dekf_reset_instances, mhe_epoch_core.h)
 #include <hip/hip_runtime.h>
 
 #include "cfg.h"
@@ -18,6 +19,7 @@
 #include "kf_core.h"
 #include "mhe_assemble_core.h"
 #include "mhe_direct_core.h"
+#include "mhe_epoch_core.h"
 #include "mhe_solve_core.h"
 
 using namespace dekf;
@@ -142,6 +144,21 @@ __global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_marginalize_early(De
     extern __shared__ double lds[];
     marginalize_early(c, s, blockIdx.x, T, lds);
 }
+
+// A direct handle that has restarted an instance (dekf_reset_instances) launches these in place of k_ekf_tick, k_mhe_assemble and
+// k_mhe_marginalize_early: the same cores on every instance's local step (mhe_epoch_core.h).  t0, c0: the epochs, [B] each.
+__global__ void __launch_bounds__(64) k_ekf_tick_ep(DevCfg c, DevState s, int count, const int* c0) {
+    int b = blockIdx.x * 64 + threadIdx.x;
+    if (b < c.B) ekf_tick_epoch(c, s, b, count, c0);
+}
+__global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_assemble_ep(DevCfg c, DevState s, int T, int pushes, const int* t0) {
+    extern __shared__ double lds[];
+    assemble_epoch(c, s, blockIdx.x, T, pushes, t0, lds);
+}
+__global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_marginalize_early_ep(DevCfg c, DevState s, int T, const int* t0) {
+    extern __shared__ double lds[];
+    marginalize_early_epoch(c, s, blockIdx.x, T, t0, lds);
+}
 #endif  // DEKF_MISC_KERNELS
 
 // The solve kernels (solve_kernels.def).  One workgroup of DEKF_SOLVE_THREADS lanes (4 wavefronts, one per SIMD of the CU) per
@@ -200,6 +217,29 @@ __global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_marginalize_early(De
 // in the same launch; win: the window stores (mhe_direct_core.h: DirectWindow).  NAME itself is the instantiation it was.
 // And the twin of that, NAME_smooth_cross (dekf_set_window_cross): the CROSS instantiation, whose backward pass also leaves the lag-one and
 // to-newest cross-covariances; cross: the store of the latter (DirectCross).  NAME and NAME_smooth are the instantiations they were.
+// And every one of the three has its epoch twin NAME_ep, NAME_smooth_ep, NAME_smooth_cross_ep, which a handle launches once
+// dekf_reset_instances has restarted an instance: it takes the handle's step T in place of (kstart, K), reads its instance's epoch
+// t0[blockIdx.x] (one scalar load per workgroup) and calls the instantiation its sibling calls on the instance's local window, or
+// nothing at the instance's local step 0 (mhe_epoch_core.h).  The three siblings are the code they were.
+#define DEKF_DIRECT_EPOCH_TWINS_(NAME, L, FT)                                                                                 \
+    __global__ void __launch_bounds__(64) NAME##_ep(DevCfg c, DevState s, int T, double* cov, const int* t0) {               \
+        extern __shared__ double lds[];                                                                                      \
+        int kstart, K;                                                                                                       \
+        if (direct_window_epoch(c, T, t0[blockIdx.x], kstart, K)) direct_solve_t<L, FT>(c, s, blockIdx.x, kstart, K, lds, cov); \
+    }                                                                                                                        \
+    __global__ void __launch_bounds__(64) NAME##_smooth_ep(DevCfg c, DevState s, int T, double* cov, DirectWindow win, const int* t0) { \
+        extern __shared__ double lds[];                                                                                      \
+        int kstart, K;                                                                                                       \
+        if (direct_window_epoch(c, T, t0[blockIdx.x], kstart, K))                                                            \
+            direct_solve_t<L, FT, true>(c, s, blockIdx.x, kstart, K, lds, cov, win);                                          \
+    }                                                                                                                        \
+    __global__ void __launch_bounds__(64) NAME##_smooth_cross_ep(DevCfg c, DevState s, int T, double* cov, DirectWindow win, \
+                                                                 DirectCross cross, const int* t0) {                         \
+        extern __shared__ double lds[];                                                                                      \
+        int kstart, K;                                                                                                       \
+        if (direct_window_epoch(c, T, t0[blockIdx.x], kstart, K))                                                            \
+            direct_solve_t<L, FT, true, true>(c, s, blockIdx.x, kstart, K, lds, cov, win, cross);                             \
+    }
 #define DEKF_DIRECT_KERNEL(NAME, L, FT, NFIX)                                                                                 \
     __global__ void __launch_bounds__(64) NAME(DevCfg c, DevState s, int kstart, int K, double* cov) {                         \
         extern __shared__ double lds[];                                                                                      \
@@ -213,14 +253,18 @@ __global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_marginalize_early(De
                                                               DirectCross cross) {                                           \
         extern __shared__ double lds[];                                                                                      \
         direct_solve_t<L, FT, true, true>(c, s, blockIdx.x, kstart, K, lds, cov, win, cross);                                 \
-    }
+    }                                                                                                                        \
+    DEKF_DIRECT_EPOCH_TWINS_(NAME, L, FT)
 #ifdef DEKF_KSET_ONLY
 #define DEKF_DIRECT_KERNEL_OFF(...)
 #else
 #define DEKF_DIRECT_KERNEL_OFF(NAME, ...)                               \
     __global__ void NAME(DevCfg, DevState, int, int, double*) {}        \
     __global__ void NAME##_smooth(DevCfg, DevState, int, int, double*, DirectWindow) {} \
-    __global__ void NAME##_smooth_cross(DevCfg, DevState, int, int, double*, DirectWindow, DirectCross) {}
+    __global__ void NAME##_smooth_cross(DevCfg, DevState, int, int, double*, DirectWindow, DirectCross) {} \
+    __global__ void NAME##_ep(DevCfg, DevState, int, double*, const int*) {} \
+    __global__ void NAME##_smooth_ep(DevCfg, DevState, int, double*, DirectWindow, const int*) {} \
+    __global__ void NAME##_smooth_cross_ep(DevCfg, DevState, int, double*, DirectWindow, DirectCross, const int*) {}
 #endif
 #include "direct_kernels.def"
 
@@ -277,6 +321,18 @@ __global__ void __launch_bounds__(256) k_ekf_cov_out(DevCfg c, DevState s, doubl
     if (e >= 16 * B) return;
     const size_t b = e / 16, i = e - 16 * b;
     out[e] = s.ekf_P[i * B + b];
+}
+
+// dekf_reset_instances: reset_instance (mhe_epoch_core.h) for the instances of the mask; cov: the handle's Cov(x_T) store
+__global__ void k_reset_instances(DevCfg c, DevState s, const int* mask, double* cov, int* t0, int* c0, int next_T, int ekf_count) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= c.B || !mask[b]) return;
+    reset_instance(c, s, b, cov, t0, c0, next_T, ekf_count);
+}
+// the host has folded its EKF tick count from count_old to count_new (dekf_ekf_step): every epoch follows (fold_epoch)
+__global__ void k_fold_epochs(int* c0, int B, int count_old, int count_new, int H) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) c0[b] = fold_epoch(c0[b], count_old, count_new, H);
 }
 
 __global__ void k_reset_state(DevCfg c, DevState s) {

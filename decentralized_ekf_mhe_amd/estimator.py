@@ -156,6 +156,20 @@ class BatchedEstimator:
         capi.check(self.lib.dekf_reset(self.h))
         self.T = 0
 
+    def reset_instances(self, mask):
+        """restart the instances whose mask entry is 1 (dekf_reset_instances; a direct handle, between update(T - 1) and the pushes of
+        step T): they start over with the next samples while every other instance keeps running.  mask: int32 [B], numpy or a torch
+        CUDA tensor (which must be complete on its stream)"""
+        p, w = _ptr_where(mask, np.int32)
+        capi.check(self.lib.dekf_reset_instances(self.h, p, w))
+
+    def instance_ticks(self):
+        """int32 [B]: the local step of every instance at the last update (dekf_get_instance_ticks): T, or T - T0 for an instance
+        restarted before step T0; its window then holds min(ticks + 1, N) steps"""
+        t = np.zeros(self.batch, np.int32)
+        capi.check(self.lib.dekf_get_instance_ticks(self.h, C.c_void_p(t.ctypes.data), capi.DEKF_HOST))
+        return t
+
     def sync(self):
         capi.check(self.lib.dekf_sync(self.h))
 
@@ -206,7 +220,8 @@ class BatchedEstimator:
 
     def window(self):
         """(K, x_win [B, K, ns], cov_win [B, K, ns, ns]) of the last update of a smoothing handle (dekf_get_window): the K = min(T + 1, N)
-        states of the window it solved, oldest first, and their covariances"""
+        states of the window it solved, oldest first, and their covariances.  After reset_instances K is the largest window of the
+        batch and instance b's first min(instance_ticks()[b] + 1, N) entries are its window"""
         ns, N = self.params.dim_state, self.params.N
         xw, cw = np.zeros((self.batch, N, ns)), np.zeros((self.batch, N, ns, ns))
         K = C.c_int(0)

@@ -337,6 +337,40 @@ dekf_status dekf_get_window(dekf_handle h, int* steps, double* x_win, double* co
 dekf_status dekf_set_window_cross(dekf_handle h, int on);
 dekf_status dekf_get_window_cross(dekf_handle h, int* steps, double* cov_lag1, double* cov_newest, dekf_mem where);
 
+/* ---- restarting single instances (direct handles): one robot starts over, the others keep running ----------------------
+ * Two more additive symbols: DEKF_ABI_VERSION and dekf_params are unchanged, and a caller that never calls them gets exactly the
+ * results (and bits) of before.  dekf_reset clears all B instances and asks for a new dekf_initialize; dekf_reset_instances restarts
+ * the instances of a mask (a rebooted robot, an estimator whose arrival cost a NaN sample has poisoned, one environment of a
+ * vectorised simulator) while every other instance keeps its window, its arrival cost and every bit of every output.
+ * dekf_reset_instances(h, mask, where): mask[B], 1 restarts the instance, 0 leaves it alone; a host or a device pointer (a device mask
+ * is copied to the host and waited for: the call checks it).
+ *  - When: on an initialised direct handle between dekf_update(h, T0 - 1) and the pushes of step T0, i.e. before that step's
+ *    dekf_ekf_step.  DEKF_ERR_ORDER before dekf_initialize.  DEKF_ERR_INVALID for a null handle or mask, for a handle that is not a
+ *    direct handle (ADMM, KF) or has solve_pipeline = 1, and for a mask entry other than 0 or 1.  The handle's stream waits for what
+ *    dekf_reset waits for (solves in flight, the arrival cost computed ahead, readers of v_b) before the instances are cleared.
+ *  - A restarted instance is as after dekf_reset: EKF state and covariance at their initial values, VO latches, way points and the
+ *    p_vo accumulator cleared, x_mhe and v_b 0, status DEKF_SOLVE_NONE, solver info 0; its block of dekf_get_mhe_cov is NaN until its
+ *    first solve.  A sample latched before the call is dropped for it; the samples pushed after the call are its first.
+ *  - Its next dekf_ekf_step is its EKF tick 0; dekf_update(h, T0) is its dekf_initialize (first sample, prior as arrival cost, no
+ *    solve) and dekf_update(h, T0 + j) its update(j), with a window of K_b = min(j + 1, N) steps.
+ *  - From step T0 on every output of the instance (dekf_get, dekf_get_ekf_cov, dekf_get_mhe_cov, dekf_get_solver_info and the first K_b
+ *    entries of dekf_get_window and dekf_get_window_cross) is bit-identical to the same instance of a fresh handle that is fed the same
+ *    samples from step T0 on.  The instances outside the mask keep every bit of every output at every later step.
+ *  - An all-zero mask changes nothing.  An instance may be restarted again at any later step, inside its own window fill too.
+ *  - *steps of dekf_get_window and dekf_get_window_cross becomes the largest K_b of the batch; entries k >= K_b of instance b (k >= K_b - 1
+ *    of cov_lag1) are not specified.  The two getters return DEKF_ERR_ORDER while no instance has solved since its restart.
+ *  - Until the first call with a non-zero mask the handle launches exactly the kernels it launched before this interface existed.
+ *    After it, and until dekf_reset, it launches their epoch twins, which take every instance's own step: dekf_solve_kernel_name then
+ *    names k_mhe_solve_direct_*_ep, *_smooth_ep or *_smooth_cross_ep.  dekf_reset clears every epoch: a handle reset and run again is
+ *    a fresh handle.
+ * dekf_get_instance_ticks(h, ticks, where): ticks[B], the local step of every instance at the last update: T on a handle that never
+ * restarted one, T - T0 after a restart before step T0 (-1 between the restart and dekf_update(h, T0)); K_b = min(ticks[b] + 1, N)
+ * once ticks[b] >= 1.  Any initialised handle; DEKF_ERR_ORDER before dekf_initialize, DEKF_ERR_INVALID for a null handle or pointer.
+ * Not part of this interface: ADMM handles (their launch takes one window length for the batch), KF and pipelined handles, instances
+ * that are switched off, parameters per instance. */
+dekf_status dekf_reset_instances(dekf_handle h, const int* mask, dekf_mem where);
+dekf_status dekf_get_instance_ticks(dekf_handle h, int* ticks, dekf_mem where);
+
 /* status[B] values written by dekf_update */
 #define DEKF_SOLVE_NONE 0       /* no solve yet (T = 0) */
 #define DEKF_SOLVE_OK 1         /* OSQP_SOLVED */

@@ -14,7 +14,11 @@ direct_smooth, direct_cross, ...) and reports each mode's best steps_per_s and l
 alternate inside one process, so that a drift of the machine does not land on one of them.
     python tools/direct_bench.py [shape ...] [--steps 200] [--modes cold,warm,direct] [--repeat 1] [--out FILE]
     python tools/direct_bench.py --modes direct,direct_smooth --repeat 3          # the smoother against its yardstick
-    python tools/direct_bench.py --modes direct,direct_smooth,direct_cross --repeat 3   # the cross-covariances against theirs"""
+    python tools/direct_bench.py --modes direct,direct_smooth,direct_cross --repeat 3   # the cross-covariances against theirs
+--epoch measures what dekf_reset_instances costs the instances it does not restart: per mode ONE handle runs the unchanged direct
+kernel (`before`), then restarts instance 0, lets its window refill and runs the epoch twins (`after`); dekf_reset brings the handle
+back, and the two alternate --repeat times in one process.  One JSON line per shape (--out: profiles/r11_epoch_bench.jsonl).
+    python tools/direct_bench.py go1 --epoch --modes direct,direct_smooth,direct_cross --steps 80 --repeat 3"""
 import argparse
 import json
 import os
@@ -75,6 +79,71 @@ def one(p, B, sd, W, steps, mode):
             "solved_fraction": solved, "kernel": kernel}
 
 
+def timed(est, sd, k0, steps, B):
+    """`steps` steps from tick k0 without events, then `steps` more with events around every launch: (steps/s, ms per launch by class)"""
+    est.sync()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for k in range(k0, k0 + steps):
+        est.push_stream_step(sd, k)
+        est.step(k)
+    est.sync()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    est.timing_enable(1)
+    est.timing_read()
+    for k in range(k0 + steps, k0 + 2 * steps):
+        est.push_stream_step(sd, k)
+        est.step(k)
+    tim = est.timing_read()
+    est.timing_enable(0)
+    return {"steps_per_s": B * steps / dt, "kernel": est.solve_kernel_name(True),
+            **{f"{c}_ms": tim[c][0] / max(tim[c][1], 1) for c in ("solve", "assemble", "ekf")}}
+
+
+def epoch_ticks(p, steps):
+    """(W, refill, log length) of epoch_runs: warm-up, the restarted instance's window fill, and everything"""
+    W, refill = max(p.N + 10, 64), p.N + 10
+    return W, refill, W + 2 * steps + refill + 2 * steps
+
+
+def epoch_runs(p, B, sd, steps, mode, repeat):
+    """before / after a first dekf_reset_instances on one handle, `repeat` times in turn (dekf_reset in between)"""
+    import numpy as np
+    W, refill, _ = epoch_ticks(p, steps)
+    est = BatchedEstimator(p, B, **MODES[mode])
+    mask = np.zeros(B, np.int32)
+    mask[0] = 1
+    before, after = [], []
+    for _ in range(repeat):
+        est.reset()
+        for k in range(W):
+            est.push_stream_step(sd, k)
+            est.step(k)
+        before.append(timed(est, sd, W, steps, B))
+        k1 = W + 2 * steps
+        est.reset_instances(mask)
+        for k in range(k1, k1 + refill):
+            est.push_stream_step(sd, k)
+            est.step(k)
+        assert int(est.instance_ticks()[0]) == refill - 1 >= p.N
+        after.append(timed(est, sd, k1 + refill, steps, B))
+        assert float((est.get()["status"] == 1).mean()) == 1.0
+    est.close()
+
+    def best(runs):
+        out = dict(max(runs, key=lambda r: r["steps_per_s"]))
+        for c in ("solve", "assemble", "ekf"):
+            out[f"{c}_ms"] = min(r[f"{c}_ms"] for r in runs)
+        out["all_steps_per_s"] = [r["steps_per_s"] for r in runs]
+        out["all_solve_ms"] = [r["solve_ms"] for r in runs]
+        return out
+    b, a = best(before), best(after)
+    return {"before": b, "after": a, "solve_ms_after_over_before": a["solve_ms"] / b["solve_ms"],
+            "assemble_ms_after_over_before": a["assemble_ms"] / b["assemble_ms"], "ekf_ms_after_over_before": a["ekf_ms"] / b["ekf_ms"],
+            "steps_per_s_after_over_before": a["steps_per_s"] / b["steps_per_s"]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("shapes", nargs="*", default=list(SHAPES))
@@ -82,8 +151,11 @@ def main():
     ap.add_argument("--modes", default="cold,warm,direct")
     ap.add_argument("--repeat", type=int, default=1)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--epoch", action="store_true", help="the same handle before and after a first dekf_reset_instances")
     a = ap.parse_args()
     modes = a.modes.split(",")
+    if a.out is None and a.epoch:
+        a.out = os.path.join(ROOT, "profiles", "r11_epoch_bench.jsonl")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "r10_cross_bench.jsonl" if "direct_cross" in modes else
                              "r09_smoother_bench.jsonl" if "direct_smooth" in modes else "r08_direct_bench.jsonl")
@@ -93,6 +165,16 @@ def main():
         p.ekf_rate = p.rate
         for k, v in kw.items():
             setattr(p, k, v)
+        if a.epoch:
+            sd = streams_to_device(make_streams(p, B, epoch_ticks(p, a.steps)[2]))
+            line = {"shape": name, "batch": B, "N": int(p.N), "steps": a.steps, "repeat": a.repeat, "epoch": True}
+            line.update({mode: epoch_runs(p, B, sd, a.steps, mode, a.repeat) for mode in modes})
+            print(json.dumps(line), flush=True)
+            with open(a.out, "a") as f:
+                f.write(json.dumps(line) + "\n")
+            del sd
+            torch.cuda.empty_cache()
+            continue
         W = max(p.N + 10, 64)  # (as tools/bench_shapes.py: past the window fill and the first vision intervals)
         sd = streams_to_device(make_streams(p, B, W + a.steps))
         line = {"shape": name, "batch": B, "N": int(p.N), "steps": a.steps}
