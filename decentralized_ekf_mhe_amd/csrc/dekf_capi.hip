@@ -2,7 +2,6 @@
 // No CPU fallback: without a usable HIP device dekf_create fails with DEKF_ERR_NO_DEVICE.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
-
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -77,15 +76,16 @@ struct dekf_handle_s {
     // staging for host-side pushes / gets
     void* stage = nullptr;
     size_t stage_bytes = 0;
+    // What a step launches is said once, by solve_launch(), from the settings and these fields.  The ADMM solve: the catalogue's row
+    // (solve_kernels.def) of the window-fill kernel and its grid ...
+    const SolveKernel* solve_entry = nullptr;
     int solve_grid = 0, gws_len = 0;
-    void (*solve_kernel)(DevCfg, DevState, int, int, int) = nullptr;
-    // full windows (K == N) of the fixed-horizon shapes: the three-workgroups-per-CU kernel (kernels.hip), its own grid and LDS size
-    void (*solve_kernel_full)(DevCfg, DevState, int, int, int) = nullptr;
+    // ... and for full windows (K == N) of the shapes that have one, the row of the kernel with more workgroups per CU (kernels.hip),
+    // its own grid, workgroup size and LDS size
+    const SolveKernel* solve_entry_full = nullptr;
     int solve_grid_full = 0;
     int solve_threads_full = DEKF_SOLVE_THREADS;  // (the four-per-CU kernels: DEKF_R4_THREADS)
     size_t lds_solve_full = 0;
-    const char *solve_name = nullptr, *solve_name_full = nullptr;  // kernel symbols, for dekf_solve_kernel_name
-    const SolveKernel* solve_entry_full = nullptr;  // the catalogue's row of solve_kernel_full (its warm twin: dekf_set_warm_start)
     // dekf_set_solver: DEKF_SOLVER_ADMM (0) or DEKF_SOLVER_DIRECT (1).  A direct handle launches `direct` (one wavefront per instance,
     // a grid of B) wherever an in-order ADMM handle launches its solve, and keeps Cov(x_T) of the last update in mhe_cov ([B][ns][ns])
     int solver = DEKF_SOLVER_ADMM;
@@ -167,27 +167,36 @@ dekf_status fail(dekf_status st, const char* msg) {
     return st;
 }
 
-// The solve kernels as dekf_create selects them: every row of solve_kernels.def with its polishing twin
+// a failed step of an entry point is the entry point's status (the message is in g_err)
+#define TRY(expr) do { if (dekf_status st_ = (expr)) return st_; } while (0)
+
+// The solve kernels as dekf_create selects them: every row of solve_kernels.def with its twins, by [warm][polish]
 typedef void (*SolveFn)(DevCfg, DevState, int, int, int);
 enum class SolveRole { ll, lg, gg, foot_lg, foot_gg, r3, r4, rr };
 struct SolveKernel {
     SolveRole role;
     int legs, nfix;  // solve_window_t's L and NFIX (0: run-time horizon)
-    SolveFn fn, fn_pol;
-    const char *name, *name_pol;
-    bool warm_twin;  // a warm handle launches fn_warm / fn_warm_pol instead (solve_kernels.def: DEKF_WARM_TWIN_<role>)
-    SolveFn fn_warm, fn_warm_pol;
-    const char *name_warm, *name_warm_pol;
+    bool warm_twin;  // a warm handle launches fn[1][.] (solve_kernels.def: DEKF_WARM_TWIN_<role>); every other row's fn[0][.] carries the warm start
+    SolveFn fn[2][2];
+    const char* name[2][2];
 };
 #define DEKF_LEGS_(L, ...) L
 #define DEKF_NFIX_(L, FACTOR_LDS, PA_LDS, NFIX, ...) NFIX
 #define DEKF_WARM_TWIN_OF_(ROLE) DEKF_WARM_TWIN_##ROLE
-#define DEKF_SOLVE_KERNEL(NAME, ROLE, THREADS, WAVES, LOOP, ...)                                                   \
-    {SolveRole::ROLE, DEKF_LEGS_(__VA_ARGS__), DEKF_NFIX_(__VA_ARGS__, 0, 0), NAME, NAME##_pol, #NAME, #NAME "_pol", \
-     DEKF_WARM_TWIN_OF_(ROLE) != 0, NAME##_warm, NAME##_warm_pol, #NAME "_warm", #NAME "_warm_pol"},
+#define DEKF_SOLVE_KERNEL(NAME, ROLE, THREADS, WAVES, LOOP, ...)                                                 \
+    {SolveRole::ROLE, DEKF_LEGS_(__VA_ARGS__), DEKF_NFIX_(__VA_ARGS__, 0, 0), DEKF_WARM_TWIN_OF_(ROLE) != 0,      \
+     {{NAME, NAME##_pol}, {NAME##_warm, NAME##_warm_pol}}, {{#NAME, #NAME "_pol"}, {#NAME "_warm", #NAME "_warm_pol"}}},
 const SolveKernel solve_kernels[] = {
 #include "solve_kernels.def"
 };
+
+// The twin of row k that a handle with these settings launches, picked here and nowhere else.  osqp.polish: the twin with the polishing
+// step; warm (dekf_set_warm_start): the twin with the warm start, of a full-window kernel whose register budget left that code out
+struct SolveTwin { SolveFn fn; const char* name; };
+SolveTwin solve_twin(const SolveKernel* k, bool polish, bool warm) {
+    const int w = warm && k->warm_twin, p = polish;
+    return {k->fn[w][p], k->name[w][p]};
+}
 
 // the kernel of ROLE for L legs: the one compiled for the horizon N if there is one, else the one with a run-time horizon
 const SolveKernel* solve_kernel(SolveRole role, int L, int N) {
@@ -207,23 +216,22 @@ typedef void (*DirectCrossFn)(DevCfg, DevState, int, int, double*, DirectWindow,
 typedef void (*DirectEpochFn)(DevCfg, DevState, int, double*, const int*);
 typedef void (*DirectSmoothEpochFn)(DevCfg, DevState, int, double*, DirectWindow, const int*);
 typedef void (*DirectCrossEpochFn)(DevCfg, DevState, int, double*, DirectWindow, DirectCross, const int*);
+// the six kernels of a row: the direct solve, its smoothing twin (dekf_set_smoother), the twin with the window cross-covariances
+// (dekf_set_window_cross), and the epoch twins of the three (dekf_reset_instances)
+enum DirectVariant { plain, smooth, cross, plain_ep, smooth_ep, cross_ep };
 struct DirectKernel {
     int legs, ft, nfix;  // direct_solve_t's L and FT; the horizon the row is meant for (0: any)
     DirectFn fn;
-    const char* name;
-    DirectSmoothFn fn_smooth;  // the smoothing twin (dekf_set_smoother)
-    const char* name_smooth;
-    DirectCrossFn fn_cross;  // the twin with the window cross-covariances (dekf_set_window_cross)
-    const char* name_cross;
-    // the epoch twins of the three (dekf_reset_instances)
+    DirectSmoothFn fn_smooth;
+    DirectCrossFn fn_cross;
     DirectEpochFn fn_ep;
     DirectSmoothEpochFn fn_smooth_ep;
     DirectCrossEpochFn fn_cross_ep;
-    const char *name_ep, *name_smooth_ep, *name_cross_ep;
+    const char* name[6];  // by DirectVariant
 };
-#define DEKF_DIRECT_KERNEL(NAME, L, FT, NFIX)                                                                          \
-    {L, FT, NFIX, NAME, #NAME, NAME##_smooth, #NAME "_smooth", NAME##_smooth_cross, #NAME "_smooth_cross",             \
-     NAME##_ep, NAME##_smooth_ep, NAME##_smooth_cross_ep, #NAME "_ep", #NAME "_smooth_ep", #NAME "_smooth_cross_ep"},
+#define DEKF_DIRECT_KERNEL(NAME, L, FT, NFIX)                                                                                \
+    {L, FT, NFIX, NAME, NAME##_smooth, NAME##_smooth_cross, NAME##_ep, NAME##_smooth_ep, NAME##_smooth_cross_ep,              \
+     {#NAME, #NAME "_smooth", #NAME "_smooth_cross", #NAME "_ep", #NAME "_smooth_ep", #NAME "_smooth_cross_ep"}},
 const DirectKernel direct_kernels[] = {
 #include "direct_kernels.def"
 };
@@ -237,6 +245,30 @@ const DirectKernel* direct_kernel(int L, int ft, int N) {
         if (k.nfix == 0) any = &k;
     }
     return any;
+}
+
+// the kernel of its row that a direct handle launches: the smoother and cross settings pick the twin, and a handle that has restarted
+// an instance (epochs) launches the epoch twin of that one, which finds every instance's window from the step
+DirectVariant direct_variant(const dekf_handle_s* h) {
+    const int v = !h->smoother ? plain : (h->cross ? cross : smooth);
+    return (DirectVariant)(h->epochs ? v + plain_ep : v);
+}
+
+// The solve launch of a step with a window of K steps: what dekf_update launches, dekf_solve_kernel_name names and dekf_launch_info
+// counts.  A function of fields the setters keep: no HIP call, nothing allocated.
+struct SolveLaunch {
+    const char* name;  // the kernel's symbol
+    int grid, threads; size_t lds;
+    SolveFn admm;           // the ADMM kernel; null on a direct handle, which launches ...
+    DirectVariant variant;  // ... this kernel of its row (h->direct)
+};
+SolveLaunch solve_launch(const dekf_handle_s* h, int K) {
+    const DirectVariant v = direct_variant(h);
+    if (h->solver == DEKF_SOLVER_DIRECT) return {h->direct->name[v], h->c.B, 64, h->lds_direct, nullptr, v};
+    const bool full = h->solve_entry_full && K == h->c.N;
+    const SolveTwin t = solve_twin(full ? h->solve_entry_full : h->solve_entry, h->c.polish != 0, h->c.warm != 0);
+    if (full) return {t.name, h->solve_grid_full, h->solve_threads_full, h->lds_solve_full, t.fn, v};
+    return {t.name, h->solve_grid, DEKF_SOLVE_THREADS, h->lds_solve, t.fn, v};
 }
 
 // A family of full-window kernels (K == N): the shapes it covers are the rows of its role in solve_kernels.def
@@ -257,7 +289,7 @@ struct FullWindowFamily {
 bool take_full_window(dekf_handle h, const FullWindowFamily& f, const SolveLayout& lay, int per_cu, int cap, int cus, int batch) {
     const SolveKernel* k = f.eligible && !h->c.ft ? solve_kernel(f.role, h->c.L, h->c.N) : nullptr;
     if (!k) return false;
-    const SolveFn fn = h->c.polish ? k->fn_pol : k->fn;
+    const SolveFn fn = solve_twin(k, h->c.polish != 0, false).fn;
     // the kernel's static LDS (reduction scratch of wave.h) counts against the same allocation as the dynamic part
     hipFuncAttributes fa;
     size_t static_lds = 512;
@@ -280,11 +312,9 @@ bool take_full_window(dekf_handle h, const FullWindowFamily& f, const SolveLayou
     if (f.ab_round5_env && getenv(f.ab_round5_env)) take = take && grid > h->solve_grid;
 #endif
     if (!take) return false;
-    h->solve_kernel_full = fn;
-    h->solve_name_full = h->c.polish ? k->name_pol : k->name;
     h->solve_entry_full = k;
-    if (k->warm_twin && f.lds > 64 * 1024)
-        (void)hipFuncSetAttribute((const void*)(h->c.polish ? k->fn_warm_pol : k->fn_warm), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds);
+    if (k->warm_twin && f.lds > 64 * 1024)  // (the twin a warm handle launches: dekf_set_warm_start)
+        (void)hipFuncSetAttribute((const void*)solve_twin(k, h->c.polish != 0, true).fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds);
     h->solve_grid_full = grid;
     h->solve_threads_full = f.threads;
     h->lds_solve_full = f.lds;
@@ -300,6 +330,20 @@ dekf_status ensure_stage(dekf_handle h, size_t bytes) {
     h->stage_bytes = bytes;
     return DEKF_OK;
 }
+// the host array *src -> the staging block at byte offset `at` (after ensure_stage), on the handle's stream; *src becomes its device address
+template <class T> dekf_status stage_in(dekf_handle h, size_t at, const T** src, size_t count) {
+    T* d = (T*)((char*)h->stage + at);
+    HIPCHK(hipMemcpyAsync(d, *src, count * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    *src = d;
+    return DEKF_OK;
+}
+
+// device memory that lives as long as the handle (dekf_destroy frees h->blocks)
+template <class T> dekf_status dev_alloc(dekf_handle h, size_t bytes, T** out) {
+    HIPCHK(hipMalloc((void**)out, bytes));
+    h->blocks.push_back(*out);
+    return DEKF_OK;
+}
 
 // dst (device) <- src (host or device), n bytes, on the handle's stream
 dekf_status put(dekf_handle h, void* dst, const void* src, size_t n, dekf_mem where) {
@@ -310,6 +354,19 @@ dekf_status put(dekf_handle h, void* dst, const void* src, size_t n, dekf_mem wh
 dekf_status fetch(dekf_handle h, void* dst, const void* src, size_t n, dekf_mem where) {
     if (!dst) return DEKF_OK;
     HIPCHK(hipMemcpyAsync(dst, src, n, where == DEKF_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
+    return DEKF_OK;
+}
+// the first `width` bytes of each of B rows `pitch` bytes apart, the pitch the same on both sides: the written entries of a window store.
+// Full rows are one contiguous copy (hipMemcpy2DAsync with the width equal to the pitch may take another copy path: not measured)
+dekf_status fetch_rows(dekf_handle h, void* dst, const void* src, size_t pitch, size_t width, size_t B, dekf_mem where) {
+    if (!dst) return DEKF_OK;
+    if (width == pitch) return fetch(h, dst, src, B * pitch, where);
+    HIPCHK(hipMemcpy2DAsync(dst, pitch, src, pitch, width, B, where == DEKF_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
+    return DEKF_OK;
+}
+// the end of a getter: what it copied to the host is there when it returns; device copies stay in stream order
+dekf_status host_sync(dekf_handle h, dekf_mem where) {
+    if (where == DEKF_HOST) HIPCHK(hipStreamSynchronize(h->stream));
     return DEKF_OK;
 }
 
@@ -342,6 +399,17 @@ dekf_status await_results(dekf_handle h) {
     return DEKF_OK;
 }
 
+// the handle's stream waits for what a reset would race with: a solve in flight writes the outputs it clears, the early marginalisation
+// the tags (k_reset_state clears them), and an all-gather's snapshot copy on the communication stream may still be reading v_b
+dekf_status quiesce(dekf_handle h) {
+    for (int i = 0; i < 2; ++i)
+        if (h->solve_pending[i]) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_solve[i], 0)); h->solve_pending[i] = false; }
+    if (h->early_pending) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_early_done, 0)); h->early_pending = false; }
+    for (int i = 0; i < 2; ++i)
+        if (h->vb_read_pending[i]) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_vb_read[i], 0)); h->vb_read_pending[i] = false; }
+    return DEKF_OK;
+}
+
 struct Timed {  // brackets one launch with events when timing is on
     dekf_handle h;
     int cls;
@@ -363,6 +431,104 @@ struct Timed {  // brackets one launch with events when timing is on
         h->ev[cls].push_back({a, b});
     }
 };
+
+// where step T of an MHE handle runs (see the handle): the set of per-solve data, the copy of the input snapshot, the solve's stream
+struct MheStep { int T, par, snap_set; DevState sp; hipStream_t ss; };
+MheStep mhe_step(dekf_handle h, int T) {
+    const int par = h->pipelined ? (T & 1) : 0, snap_set = h->pipelined ? T % DEKF_SNAP_SETS : 0;
+    MheStep st = {T, par, snap_set, h->sp[par], h->pipelined ? h->solve_stream[par] : h->stream};
+    // The assemble writes the solve's input snapshot.  With two copies it had to wait for the solve of step T - 2, and by
+    // then step T - 1's 768 persistent workgroups hold every slot of the machine: the assemble crawled in (0.41 instead of
+    // 0.07 ms) as they left, and the solve of step T started that much late — the pipeline ran on its dependencies, not on
+    // the machine (profiles/r05_step_pipelining_timeline.txt).  With three copies it waits for step T - 3, which is long
+    // over: the small kernels of a step run while the step before the previous one drains, and the solve of step T is
+    // ready the moment a slot frees.  (Outputs and scratch slabs stay at two sets: solves on one stream are in order.)
+    if (h->pipelined) st.sp.snap = h->s.snap + (size_t)st.snap_set * h->c.snap_len * h->c.B;
+    return st;
+}
+
+// the terms of step T: waits for the snapshot copy to be free and for the arrival cost computed ahead, then the assemble
+dekf_status assemble_step(dekf_handle h, const MheStep& st) {
+    if (h->pipelined && h->snap_busy[st.snap_set]) HIPCHK(hipStreamWaitEvent(h->stream, h->ev_snap_free[st.snap_set], 0));
+    if (h->early_pending) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_early_done, 0)); h->early_pending = false; }
+    {
+        Timed t(h, 1);
+        if (h->epochs) k_mhe_assemble_ep<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->c, st.sp, st.T, h->pushes, h->ep_t0);
+        else k_mhe_assemble<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->c, st.sp, st.T, h->pushes);
+    }
+    HIPCHK(hipGetLastError());
+    if (h->early_stream) HIPCHK(hipEventRecord(h->ev_asm_done, h->stream));
+    return DEKF_OK;
+}
+
+// the launch that solve_launch describes, on stream ss
+void launch_solve(dekf_handle h, const SolveLaunch& l, const DevState& sp, int T, int kstart, int K, hipStream_t ss) {
+    if (l.admm) return (void)l.admm<<<l.grid, l.threads, l.lds, ss>>>(h->c, sp, kstart, K, h->gws_len);
+    const DirectKernel& d = *h->direct;
+    switch (l.variant) {
+    case plain: d.fn<<<l.grid, l.threads, l.lds, ss>>>(h->c, sp, kstart, K, h->mhe_cov); break;
+    case smooth: d.fn_smooth<<<l.grid, l.threads, l.lds, ss>>>(h->c, sp, kstart, K, h->mhe_cov, h->win); break;
+    case cross: d.fn_cross<<<l.grid, l.threads, l.lds, ss>>>(h->c, sp, kstart, K, h->mhe_cov, h->win, h->cross_st); break;
+    // (a direct handle that has restarted an instance: the epoch twins, which find every instance's window from the step)
+    case plain_ep: d.fn_ep<<<l.grid, l.threads, l.lds, ss>>>(h->c, sp, T, h->mhe_cov, h->ep_t0); break;
+    case smooth_ep: d.fn_smooth_ep<<<l.grid, l.threads, l.lds, ss>>>(h->c, sp, T, h->mhe_cov, h->win, h->ep_t0); break;
+    case cross_ep: d.fn_cross_ep<<<l.grid, l.threads, l.lds, ss>>>(h->c, sp, T, h->mhe_cov, h->win, h->cross_st, h->ep_t0); break;
+    }
+}
+
+// the solve of step T behind its terms, and what the getters need to know about it
+dekf_status solve_step(dekf_handle h, const MheStep& st) {
+    const int T = st.T, par = st.par;
+    const hipStream_t ss = st.ss;
+    if (h->pipelined) {
+        HIPCHK(hipEventRecord(h->ev_asm[par], h->stream));
+        HIPCHK(hipStreamWaitEvent(ss, h->ev_asm[par], 0));
+        // the all-gather of step T - 2 read THIS set's v_b until its snapshot copy was through (dekf_allgather_vb)
+        if (h->vb_read_pending[par]) { HIPCHK(hipStreamWaitEvent(ss, h->ev_vb_read[par], 0)); h->vb_read_pending[par] = false; }
+        // A recorded event between the stream-waits and the launch: measured, not understood.  Without it the solve of step
+        // T + 1 does not start under the last round of step T's solve and the mode gains nothing (2.09 M steps/s, Go1 at 4096);
+        // with it the two overlap (2.16 M).  Found because bench.py's timing events had the same effect; an event recorded only
+        // AFTER the launch does not (profiles/r05_step_pipelining_queues.txt).
+        HIPCHK(hipEventRecord(h->ev_mark[par], ss));
+    }
+    const int kstart = T - h->c.N + 1 > 0 ? T - h->c.N + 1 : 0;
+    const int K = T - kstart + 1;
+    {
+        Timed t(h, 2, ss);
+#ifdef DEKF_AB_KNOBS  // A/B builds only: a quiet gap (an empty kernel) between the term construction and the solve launch
+        { static const int gap = getenv("DEKF_DEBUG_GAP_KERNEL") ? atoi(getenv("DEKF_DEBUG_GAP_KERNEL")) : 0;
+          for (int i = 0; i < gap; ++i) k_gap<<<1, 64, 0, ss>>>(); }
+#endif
+        launch_solve(h, solve_launch(h, K), st.sp, T, kstart, K, ss);
+    }
+    if (h->pipelined) {
+        HIPCHK(hipEventRecord(h->ev_solve[par], ss));
+        h->solve_pending[par] = true;
+        HIPCHK(hipEventRecord(h->ev_snap_free[st.snap_set], ss));
+        h->snap_busy[st.snap_set] = true;
+    }
+    h->last_par = par;
+    h->mhe_cov_valid = h->solver == DEKF_SOLVER_DIRECT;
+    h->win_steps = h->smoother ? K : 0;
+    if (h->epochs && h->smoother) {  // the largest window of the batch: the instance restarted longest ago (none at its local step 0)
+        const int Tl = T - h->min_t0;
+        h->win_steps = Tl < 1 ? 0 : (Tl + 1 < h->c.N ? Tl + 1 : h->c.N);
+    }
+    return DEKF_OK;
+}
+
+// in-order mode: the arrival cost of step T + 1 on early_stream, behind the assemble of step T (the arrival cost and the records as it
+// left them), beside its solve
+dekf_status marginalize_next_early(dekf_handle h, int T) {
+    HIPCHK(hipStreamWaitEvent(h->early_stream, h->ev_asm_done, 0));
+    HIPCHK(hipEventRecord(h->ev_early_mark, h->early_stream));  // (as before a pipelined solve launch: see there)
+    if (h->epochs) k_mhe_marginalize_early_ep<<<h->c.B, 64, h->lds_asm, h->early_stream>>>(h->c, h->s, T + 1, h->ep_t0);
+    else k_mhe_marginalize_early<<<h->c.B, 64, h->lds_asm, h->early_stream>>>(h->c, h->s, T + 1);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev_early_done, h->early_stream));
+    h->early_pending = true;
+    return DEKF_OK;
+}
 
 }  // namespace
 
@@ -416,39 +582,31 @@ dekf_status dekf_create(const dekf_params* p, int batch, int device, void* strea
     // diagnostic build only: DEKF_DEBUG_LDS_PAD=<bytes> inflates the request (e.g. to force one workgroup per CU)
     if (const char* pad = getenv("DEKF_DEBUG_LDS_PAD")) h->lds_solve += (size_t)atol(pad);
 #endif
-    {
-        // the placement of the factor (SolveLayout), or the foot-position states' own family (two rows per block in the solve)
-        const SolveRole role = c.ft ? (lay.factor_in_lds() ? SolveRole::foot_lg : SolveRole::foot_gg)
-                                    : (lay.pa_in_lds() ? SolveRole::ll : (lay.factor_in_lds() ? SolveRole::lg : SolveRole::gg));
-        const SolveKernel* pick = solve_kernel(role, c.L, c.N);
-        // osqp.polish: the twin that carries the polishing step
-        h->solve_kernel = c.polish ? pick->fn_pol : pick->fn;
-        h->solve_name = c.polish ? pick->name_pol : pick->name;
+    // the placement of the factor (SolveLayout), or the foot-position states' own family (two rows per block in the solve)
+    const SolveRole role = c.ft ? (lay.factor_in_lds() ? SolveRole::foot_lg : SolveRole::foot_gg)
+                                : (lay.pa_in_lds() ? SolveRole::ll : (lay.factor_in_lds() ? SolveRole::lg : SolveRole::gg));
+    h->solve_entry = solve_kernel(role, c.L, c.N);
 #ifdef DEKF_PROFILE
-        // diagnostic build only: DEKF_DEBUG_PLACEMENT=1|2 forces the _lg / _gg placement (2 also shrinks the LDS request)
-        if (const char* pl = getenv("DEKF_DEBUG_PLACEMENT")) {
-            int p = atoi(pl);
-            if ((p == 1 || p == 2) && !c.ft) {
-                const SolveKernel* t = solve_kernel(p == 1 ? SolveRole::lg : SolveRole::gg, c.L, 0);
-                h->solve_kernel = c.polish ? t->fn_pol : t->fn;
-                h->solve_name = c.polish ? t->name_pol : t->name;
-            }
-            // the _gg kernels carve D, E, bounds and R behind the iterates when SolveLayout::gg_consts_in_lds() says so
-            if (p == 2) h->lds_solve = (size_t)(lay.vec + (lay.gg_consts_in_lds() ? lay.gg_consts() : 0)) * sizeof(double);
-            if (p == 2) h->c.gws_wt = !c.ft;
-        }
-#endif
+    // diagnostic build only: DEKF_DEBUG_PLACEMENT=1|2 forces the _lg / _gg placement (2 also shrinks the LDS request)
+    if (const char* pl = getenv("DEKF_DEBUG_PLACEMENT")) {
+        int p = atoi(pl);
+        if ((p == 1 || p == 2) && !c.ft) h->solve_entry = solve_kernel(p == 1 ? SolveRole::lg : SolveRole::gg, c.L, 0);
+        // the _gg kernels carve D, E, bounds and R behind the iterates when SolveLayout::gg_consts_in_lds() says so
+        if (p == 2) h->lds_solve = (size_t)(lay.vec + (lay.gg_consts_in_lds() ? lay.gg_consts() : 0)) * sizeof(double);
+        if (p == 2) h->c.gws_wt = !c.ft;
     }
+#endif
     h->lds_asm = (size_t)AsmScratch::len(c.L, c.ft) * sizeof(double);
     h->lds_kf = (size_t)KfScratch::len(c.L, c.ft) * sizeof(double);
     if (h->lds_solve > 160 * 1024) {
         dekf_destroy(h);
         return fail(DEKF_ERR_INVALID, "window too large: ADMM iterates exceed the 160 KiB LDS of one CU");
     }
-    if (h->lds_solve > 64 * 1024)
-        (void)hipFuncSetAttribute((const void*)h->solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_solve);
+    // (the rows of the window-fill kernels have no warm twin: this is the kernel a warm handle launches too)
+    const SolveFn fill = solve_twin(h->solve_entry, c.polish != 0, false).fn;
+    if (h->lds_solve > 64 * 1024) (void)hipFuncSetAttribute((const void*)fill, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_solve);
     int per_cu = 1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)h->solve_kernel, DEKF_SOLVE_THREADS, h->lds_solve) != hipSuccess || per_cu < 1)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)fill, DEKF_SOLVE_THREADS, h->lds_solve) != hipSuccess || per_cu < 1)
         per_cu = 1;
     const int cap = p->solve_workgroups_per_cu;  // 0: no cap
     if (cap > 0 && per_cu > cap) per_cu = cap;
@@ -472,7 +630,7 @@ dekf_status dekf_create(const dekf_params* p, int batch, int device, void* strea
     };
     for (const FullWindowFamily& f : families)
         if (take_full_window(h, f, lay, per_cu, cap, prop.multiProcessorCount, batch)) break;
-    const int solve_slots = h->solve_kernel_full && h->solve_grid_full > h->solve_grid ? h->solve_grid_full : h->solve_grid;
+    const int solve_slots = h->solve_entry_full && h->solve_grid_full > h->solve_grid ? h->solve_grid_full : h->solve_grid;
     Gws g;
     g.init(c.N, c.L, c.ft, h->c.gws_wt);
     h->gws_len = g.total;
@@ -481,9 +639,8 @@ dekf_status dekf_create(const dekf_params* p, int batch, int device, void* strea
     alloc_state(h->c, h->s, solve_slots, [&](size_t bytes) -> void* {
         void* q = nullptr;
         if (!ok) return nullptr;
-        if (hipMalloc(&q, bytes ? bytes : 8) != hipSuccess) { ok = false; return nullptr; }
+        if (dev_alloc(h, bytes ? bytes : 8, &q) != DEKF_OK) { ok = false; return nullptr; }
         if (hipMemsetAsync(q, 0, bytes ? bytes : 8, h->stream) != hipSuccess) ok = false;
-        h->blocks.push_back(q);
         return q;
     }, h->pipelined ? 2 : 1);
     if (!ok) {
@@ -492,11 +649,11 @@ dekf_status dekf_create(const dekf_params* p, int batch, int device, void* strea
     }
     h->sp[0] = h->s;
     h->sp[1] = h->pipelined ? second_set(h->c, h->s, solve_slots) : h->s;
+    int prio_least = 0, prio_greatest = 0;  // (of the streams the two modes create below)
+    (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
     // (N = 1: the record folded at step T gets its gains AT step T.  DEKF_DEBUG_NO_EARLY_MARGINALIZE in the environment: diagnostic switch,
     // everything on the handle's stream as before round 5 — same bits either way, tests/test_gpu_configs.py)
     if (!h->pipelined && c.est_type == 0 && c.N >= 2 && !getenv("DEKF_DEBUG_NO_EARLY_MARGINALIZE")) {
-        int prio_least = 0, prio_greatest = 0;
-        (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
         // least priority: background work that is to take the slots the solve leaves, not to compete for them when both are ready
         // (and a priority class of its own: never on a hardware queue with the caller's streams — see the solve streams below)
         if (hipStreamCreateWithPriority(&h->early_stream, hipStreamNonBlocking, prio_least) != hipSuccess ||
@@ -513,8 +670,6 @@ dekf_status dekf_create(const dekf_params* p, int batch, int device, void* strea
         // one more normal-priority stream alive in the process (another handle, idle) a solve stream shared a queue with the handle's
         // own stream and the mode ran at 1.34 M instead of 2.1 M steps/s (profiles/r05_step_pipelining_queues.txt).  In their own
         // class they share queues with nothing the caller creates by default.
-        int prio_least = 0, prio_greatest = 0;
-        (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
         for (int i = 0; i < 2 && ok; ++i) {
             ok = hipStreamCreateWithPriority(&h->solve_stream[i], hipStreamNonBlocking, prio_greatest) == hipSuccess &&
                  hipEventCreateWithFlags(&h->ev_asm[i], hipEventDisableTiming) == hipSuccess &&
@@ -573,20 +728,13 @@ dekf_status dekf_destroy(dekf_handle h) {
 dekf_status dekf_reset(dekf_handle h) {
     if (!h) return fail(DEKF_ERR_INVALID, "null handle");
     HIPCHK(hipSetDevice(h->device));
-    for (int i = 0; i < 2; ++i)   // a solve still in flight writes the outputs this clears
-        if (h->solve_pending[i]) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_solve[i], 0)); h->solve_pending[i] = false; }
-    for (int i = 0; i < DEKF_SNAP_SETS; ++i) h->snap_busy[i] = false;  // (every solve is behind the two events just waited for)
-    if (h->early_pending) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_early_done, 0)); h->early_pending = false; }  // (k_reset_state clears its tags)
-    for (int i = 0; i < 2; ++i)   // ... and an all-gather's snapshot copy on the communication stream may still be reading v_b
-        if (h->vb_read_pending[i]) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_vb_read[i], 0)); h->vb_read_pending[i] = false; }
+    TRY(quiesce(h));
+    for (int i = 0; i < DEKF_SNAP_SETS; ++i) h->snap_busy[i] = false;  // (every solve is behind the events just waited for)
     for (int i = 0; i < (h->pipelined ? 2 : 1); ++i) {
         k_reset_state<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->sp[i]);
         HIPCHK(hipGetLastError());
     }
-    h->last_par = 0;
-    h->ekf_count = 0;
-    h->pushes = 0;
-    h->next_T = 0;
+    h->last_par = h->ekf_count = h->pushes = h->next_T = 0;
     h->initialized = false;
     h->mhe_cov_valid = false;  // (the solver, smoother and cross settings survive)
     h->win_steps = 0;
@@ -622,29 +770,20 @@ dekf_status dekf_reset_instances(dekf_handle h, const int* mask, dekf_mem where)
         any = any || m[b] == 1;
     }
     if (!any) return DEKF_OK;  // nothing changes, the kernels the handle launches included
-    // what dekf_reset waits for: a solve in flight writes the outputs this clears, the early marginalisation the tags, and an
-    // all-gather's snapshot copy may still be reading v_b
-    for (int i = 0; i < 2; ++i)
-        if (h->solve_pending[i]) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_solve[i], 0)); h->solve_pending[i] = false; }
-    if (h->early_pending) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_early_done, 0)); h->early_pending = false; }
-    for (int i = 0; i < 2; ++i)
-        if (h->vb_read_pending[i]) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_vb_read[i], 0)); h->vb_read_pending[i] = false; }
+    TRY(quiesce(h));  // (what dekf_reset waits for)
     if (!h->ep_t0) {
         int* e = nullptr;  // t0 | c0 in one block
-        HIPCHK(hipMalloc(&e, 2 * B * sizeof(int)));
-        h->blocks.push_back(e);
+        TRY(dev_alloc(h, 2 * B * sizeof(int), &e));
         HIPCHK(hipMemsetAsync(e, 0, 2 * B * sizeof(int), h->stream));
         h->ep_t0 = e;
         h->ep_c0 = e + B;
         h->t0_host.assign(B, 0);
         h->min_t0 = 0;
     }
-    const int* dmask = mask;
+    const int* dmask = where == DEKF_HOST ? m.data() : mask;
     if (where == DEKF_HOST) {
-        dekf_status st = ensure_stage(h, B * sizeof(int));
-        if (st) return st;
-        HIPCHK(hipMemcpyAsync(h->stage, m.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        dmask = (const int*)h->stage;
+        TRY(ensure_stage(h, B * sizeof(int)));
+        TRY(stage_in(h, 0, &dmask, B));
     }
     k_reset_instances<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->s, dmask, h->mhe_cov, h->ep_t0, h->ep_c0, h->next_T, h->ekf_count);
     HIPCHK(hipGetLastError());
@@ -715,14 +854,11 @@ dekf_status dekf_push_go1_joints(dekf_handle h, const double* joint_position, co
     size_t B = h->c.B;
     const double *jp = joint_position, *jv = joint_velocity, *ff = foot_force;
     if (!jp || !jv || !ff) return fail(DEKF_ERR_INVALID, "null input pointer");
-    if (where == DEKF_HOST) {
-        dekf_status st = ensure_stage(h, 28 * B * 8);
-        if (st) return st;
-        double* d = (double*)h->stage;
-        HIPCHK(hipMemcpyAsync(d, jp, 12 * B * 8, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(d + 12 * B, jv, 12 * B * 8, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(d + 24 * B, ff, 4 * B * 8, hipMemcpyHostToDevice, h->stream));
-        jp = d; jv = d + 12 * B; ff = d + 24 * B;
+    if (where == DEKF_HOST) {  // jp(12) jv(12) ff(4): 28 doubles per instance
+        TRY(ensure_stage(h, 28 * B * 8));
+        TRY(stage_in(h, 0, &jp, 12 * B));
+        TRY(stage_in(h, 12 * B * 8, &jv, 12 * B));
+        TRY(stage_in(h, 24 * B * 8, &ff, 4 * B));
     }
     k_go1_leg_odometry<<<(h->c.B + 63) / 64, 64, 0, h->stream>>>(h->c, h->s, jp, jv, ff, h->prm.contact_effort_threshold,
                                                                h->prm.p_ib[0], h->prm.p_ib[1], h->prm.p_ib[2]);
@@ -737,21 +873,16 @@ dekf_status dekf_push_vo(dekf_handle h, const int* mask, const double* t_pre, co
     if ((q_vo == nullptr) != (t_pose == nullptr)) return fail(DEKF_ERR_INVALID, "t_pose and q_vo must be given together");
     size_t B = h->c.B;
     if (where == DEKF_HOST) {
-        // mask(int) t_pre t_now dp(3) t_pose q(4): 10 doubles + 1 int per instance
-        dekf_status st = ensure_stage(h, (10 * 8 + 8) * B);
-        if (st) return st;
-        double* d = (double*)h->stage;
-        int* dm = (int*)(d + 10 * B);
-        HIPCHK(hipMemcpyAsync(dm, mask, B * 4, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(d, t_pre, B * 8, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(d + B, t_now, B * 8, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(d + 2 * B, dp_body, 3 * B * 8, hipMemcpyHostToDevice, h->stream));
+        // t_pre t_now dp(3) t_pose q(4) mask(int): 10 doubles + 1 int per instance
+        TRY(ensure_stage(h, (10 * 8 + 8) * B));
+        TRY(stage_in(h, 10 * B * 8, &mask, B));
+        TRY(stage_in(h, 0, &t_pre, B));
+        TRY(stage_in(h, B * 8, &t_now, B));
+        TRY(stage_in(h, 2 * B * 8, &dp_body, 3 * B));
         if (q_vo) {
-            HIPCHK(hipMemcpyAsync(d + 5 * B, t_pose, B * 8, hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(d + 6 * B, q_vo, 4 * B * 8, hipMemcpyHostToDevice, h->stream));
+            TRY(stage_in(h, 5 * B * 8, &t_pose, B));
+            TRY(stage_in(h, 6 * B * 8, &q_vo, 4 * B));
         }
-        mask = dm; t_pre = d; t_now = d + B; dp_body = d + 2 * B;
-        if (q_vo) { t_pose = d + 5 * B; q_vo = d + 6 * B; }
     }
     k_latch_vo<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->s, mask, t_pre, t_now, dp_body, t_pose, q_vo);
     HIPCHK(hipGetLastError());
@@ -809,88 +940,11 @@ dekf_status dekf_update(dekf_handle h, int T) {
     if (!h->initialized) return fail(DEKF_ERR_ORDER, "dekf_update before dekf_initialize");
     if (T != h->next_T) return fail(DEKF_ERR_ORDER, "update(T) must be called with T = 1, 2, 3, ... (EstSub.cpp:58-75)");
     if (h->c.est_type == 0) {
-        const int par = h->pipelined ? (T & 1) : 0;
-        DevState sp = h->sp[par];
-        hipStream_t ss = h->pipelined ? h->solve_stream[par] : h->stream;
-        const int snap_set = h->pipelined ? T % DEKF_SNAP_SETS : 0;
-        if (h->pipelined) {
-            // The assemble writes the solve's input snapshot.  With two copies it had to wait for the solve of step T - 2, and by
-            // then step T - 1's 768 persistent workgroups hold every slot of the machine: the assemble crawled in (0.41 instead of
-            // 0.07 ms) as they left, and the solve of step T started that much late — the pipeline ran on its dependencies, not on
-            // the machine (profiles/r05_step_pipelining_timeline.txt).  With three copies it waits for step T - 3, which is long
-            // over: the small kernels of a step run while the step before the previous one drains, and the solve of step T is
-            // ready the moment a slot frees.  (Outputs and scratch slabs stay at two sets: solves on one stream are in order.)
-            sp.snap = h->s.snap + (size_t)snap_set * h->c.snap_len * h->c.B;
-            if (h->snap_busy[snap_set]) HIPCHK(hipStreamWaitEvent(h->stream, h->ev_snap_free[snap_set], 0));
-        }
-        if (h->early_pending) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_early_done, 0)); h->early_pending = false; }
-        {
-            Timed t(h, 1);
-            if (h->epochs) k_mhe_assemble_ep<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->c, sp, T, h->pushes, h->ep_t0);
-            else k_mhe_assemble<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->c, sp, T, h->pushes);
-        }
-        HIPCHK(hipGetLastError());
-        if (h->early_stream) HIPCHK(hipEventRecord(h->ev_asm_done, h->stream));
-        if (h->pipelined) {
-            HIPCHK(hipEventRecord(h->ev_asm[par], h->stream));
-            HIPCHK(hipStreamWaitEvent(ss, h->ev_asm[par], 0));
-            // the all-gather of step T - 2 read THIS set's v_b until its snapshot copy was through (dekf_allgather_vb)
-            if (h->vb_read_pending[par]) { HIPCHK(hipStreamWaitEvent(ss, h->ev_vb_read[par], 0)); h->vb_read_pending[par] = false; }
-            // A recorded event between the stream-waits and the launch: measured, not understood.  Without it the solve of step
-            // T + 1 does not start under the last round of step T's solve and the mode gains nothing (2.09 M steps/s, Go1 at 4096);
-            // with it the two overlap (2.16 M).  Found because bench.py's timing events had the same effect; an event recorded only
-            // AFTER the launch does not (profiles/r05_step_pipelining_queues.txt).
-            HIPCHK(hipEventRecord(h->ev_mark[par], ss));
-        }
-        int kstart = T - h->c.N + 1 > 0 ? T - h->c.N + 1 : 0;
-        {
-            Timed t(h, 2, ss);
-            const int K = T - kstart + 1;
-#ifdef DEKF_AB_KNOBS  // A/B builds only: a quiet gap (an empty kernel) between the term construction and the solve launch
-            { static const int gap = getenv("DEKF_DEBUG_GAP_KERNEL") ? atoi(getenv("DEKF_DEBUG_GAP_KERNEL")) : 0;
-              for (int i = 0; i < gap; ++i) k_gap<<<1, 64, 0, ss>>>(); }
-#endif
-            // (a direct handle that has restarted an instance: the epoch twins, which find every instance's window from the step)
-            if (h->epochs && h->smoother && h->cross)
-                h->direct->fn_cross_ep<<<h->c.B, 64, h->lds_direct, ss>>>(h->c, sp, T, h->mhe_cov, h->win, h->cross_st, h->ep_t0);
-            else if (h->epochs && h->smoother)
-                h->direct->fn_smooth_ep<<<h->c.B, 64, h->lds_direct, ss>>>(h->c, sp, T, h->mhe_cov, h->win, h->ep_t0);
-            else if (h->epochs)
-                h->direct->fn_ep<<<h->c.B, 64, h->lds_direct, ss>>>(h->c, sp, T, h->mhe_cov, h->ep_t0);
-            else if (h->solver == DEKF_SOLVER_DIRECT && h->smoother && h->cross)
-                h->direct->fn_cross<<<h->c.B, 64, h->lds_direct, ss>>>(h->c, sp, kstart, K, h->mhe_cov, h->win, h->cross_st);
-            else if (h->solver == DEKF_SOLVER_DIRECT && h->smoother)
-                h->direct->fn_smooth<<<h->c.B, 64, h->lds_direct, ss>>>(h->c, sp, kstart, K, h->mhe_cov, h->win);
-            else if (h->solver == DEKF_SOLVER_DIRECT)
-                h->direct->fn<<<h->c.B, 64, h->lds_direct, ss>>>(h->c, sp, kstart, K, h->mhe_cov);
-            else if (h->solve_kernel_full && K == h->c.N)
-                h->solve_kernel_full<<<h->solve_grid_full, h->solve_threads_full, h->lds_solve_full, ss>>>(h->c, sp, kstart, K, h->gws_len);
-            else
-                h->solve_kernel<<<h->solve_grid, DEKF_SOLVE_THREADS, h->lds_solve, ss>>>(h->c, sp, kstart, K, h->gws_len);
-        }
-        if (h->pipelined) {
-            HIPCHK(hipEventRecord(h->ev_solve[par], ss));
-            h->solve_pending[par] = true;
-            HIPCHK(hipEventRecord(h->ev_snap_free[snap_set], ss));
-            h->snap_busy[snap_set] = true;
-        }
-        h->last_par = par;
-        h->mhe_cov_valid = h->solver == DEKF_SOLVER_DIRECT;
-        h->win_steps = h->smoother ? T - kstart + 1 : 0;
-        if (h->epochs && h->smoother) {  // the largest window of the batch: the instance restarted longest ago (none at its local step 0)
-            const int Tl = T - h->min_t0;
-            h->win_steps = Tl < 1 ? 0 : (Tl + 1 < h->c.N ? Tl + 1 : h->c.N);
-        }
-        if (h->early_stream) {
-            // behind the assemble of this step (the arrival cost and the records as it left them), beside this step's solve
-            HIPCHK(hipStreamWaitEvent(h->early_stream, h->ev_asm_done, 0));
-            HIPCHK(hipEventRecord(h->ev_early_mark, h->early_stream));  // (as before a pipelined solve launch: see there)
-            if (h->epochs) k_mhe_marginalize_early_ep<<<h->c.B, 64, h->lds_asm, h->early_stream>>>(h->c, h->s, T + 1, h->ep_t0);
-            else k_mhe_marginalize_early<<<h->c.B, 64, h->lds_asm, h->early_stream>>>(h->c, h->s, T + 1);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(h->ev_early_done, h->early_stream));
-            h->early_pending = true;
-        }
+        // the terms, the solve behind them (pipelined: on its own stream), in-order: the next step's arrival cost beside the solve
+        const MheStep st = mhe_step(h, T);
+        TRY(assemble_step(h, st));
+        TRY(solve_step(h, st));
+        if (h->early_stream) TRY(marginalize_next_early(h, T));
     } else {
         Timed t(h, 1);
         k_kf_update<<<h->c.B, 64, h->lds_kf, h->stream>>>(h->c, h->s, h->pushes);
@@ -902,24 +956,21 @@ dekf_status dekf_update(dekf_handle h, int T) {
 }
 
 dekf_status dekf_step(dekf_handle h, int T) {
-    dekf_status st = dekf_ekf_step(h);
-    if (st) return st;
+    TRY(dekf_ekf_step(h));
     return T == 0 ? dekf_initialize(h) : dekf_update(h, T);
 }
 
 dekf_status dekf_get(dekf_handle h, double* x_mhe, double* v_b, double* quat, double* p_vo, int* status, dekf_mem where) {
     if (!h) return fail(DEKF_ERR_INVALID, "null handle");
     size_t B = h->c.B;
-    dekf_status st;
-    if ((st = await_results(h))) return st;
+    TRY(await_results(h));
     const DevState& s = h->sp[h->last_par];
-    if ((st = fetch(h, x_mhe, s.x_mhe, (size_t)h->c.ns * B * 8, where))) return st;
-    if ((st = fetch(h, v_b, s.v_b, 3 * B * 8, where))) return st;
-    if ((st = fetch(h, quat, s.quat, 4 * B * 8, where))) return st;
-    if ((st = fetch(h, p_vo, s.p_vo, 3 * B * 8, where))) return st;
-    if ((st = fetch(h, status, s.status, B * 4, where))) return st;
-    if (where == DEKF_HOST) HIPCHK(hipStreamSynchronize(h->stream));
-    return DEKF_OK;
+    TRY(fetch(h, x_mhe, s.x_mhe, (size_t)h->c.ns * B * 8, where));
+    TRY(fetch(h, v_b, s.v_b, 3 * B * 8, where));
+    TRY(fetch(h, quat, s.quat, 4 * B * 8, where));
+    TRY(fetch(h, p_vo, s.p_vo, 3 * B * 8, where));
+    TRY(fetch(h, status, s.status, B * 4, where));
+    return host_sync(h, where);
 }
 
 dekf_status dekf_get_ekf_cov(dekf_handle h, double* cov, dekf_mem where) {
@@ -929,40 +980,32 @@ dekf_status dekf_get_ekf_cov(dekf_handle h, double* cov, dekf_mem where) {
     const size_t B = h->c.B;
     double* dst = cov;
     if (where == DEKF_HOST) {
-        dekf_status st = ensure_stage(h, 16 * B * sizeof(double));
-        if (st) return st;
+        TRY(ensure_stage(h, 16 * B * sizeof(double)));
         dst = (double*)h->stage;
     }
     k_ekf_cov_out<<<(int)((16 * B + 255) / 256), 256, 0, h->stream>>>(h->c, h->s, dst);
     HIPCHK(hipGetLastError());
-    if (where == DEKF_HOST) {
-        HIPCHK(hipMemcpyAsync(cov, dst, 16 * B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
-    return DEKF_OK;
+    if (where == DEKF_HOST) TRY(fetch(h, cov, dst, 16 * B * sizeof(double), where));
+    return host_sync(h, where);
 }
 
 dekf_status dekf_get_solver_info(dekf_handle h, int* iters, int* rho_updates, double* pri_res, double* dua_res, dekf_mem where) {
     if (!h) return fail(DEKF_ERR_INVALID, "null handle");
     size_t B = h->c.B;
-    dekf_status st;
-    if ((st = await_results(h))) return st;
+    TRY(await_results(h));
     const DevState& s = h->sp[h->last_par];
-    if ((st = fetch(h, iters, s.iters, B * 4, where))) return st;
-    if ((st = fetch(h, rho_updates, s.rho_updates, B * 4, where))) return st;
-    if ((st = fetch(h, pri_res, s.pri_res, B * 8, where))) return st;
-    if ((st = fetch(h, dua_res, s.dua_res, B * 8, where))) return st;
-    if (where == DEKF_HOST) HIPCHK(hipStreamSynchronize(h->stream));
-    return DEKF_OK;
+    TRY(fetch(h, iters, s.iters, B * 4, where));
+    TRY(fetch(h, rho_updates, s.rho_updates, B * 4, where));
+    TRY(fetch(h, pri_res, s.pri_res, B * 8, where));
+    TRY(fetch(h, dua_res, s.dua_res, B * 8, where));
+    return host_sync(h, where);
 }
 
 dekf_status dekf_get_polish_status(dekf_handle h, int* polish_status, dekf_mem where) {
     if (!h || !polish_status) return fail(DEKF_ERR_INVALID, "null argument");
-    dekf_status st;
-    if ((st = await_results(h))) return st;
-    if ((st = fetch(h, polish_status, h->sp[h->last_par].polish_status, (size_t)h->c.B * 4, where))) return st;
-    if (where == DEKF_HOST) HIPCHK(hipStreamSynchronize(h->stream));
-    return DEKF_OK;
+    TRY(await_results(h));
+    TRY(fetch(h, polish_status, h->sp[h->last_par].polish_status, (size_t)h->c.B * 4, where));
+    return host_sync(h, where);
 }
 
 dekf_status dekf_set_warm_start(dekf_handle h, int on) {
@@ -979,10 +1022,8 @@ dekf_status dekf_set_warm_start(dekf_handle h, int on) {
         const size_t B = (size_t)h->c.B;
         double* w = nullptr;
         int* t = nullptr;
-        HIPCHK(hipMalloc(&w, B * wl.len * sizeof(double)));
-        h->blocks.push_back(w);
-        HIPCHK(hipMalloc(&t, 2 * B * sizeof(int)));
-        h->blocks.push_back(t);
+        TRY(dev_alloc(h, B * wl.len * sizeof(double), &w));
+        TRY(dev_alloc(h, 2 * B * sizeof(int), &t));
         HIPCHK(hipMemsetAsync(t, 0xff, B * sizeof(int), h->stream));  // tags -1: no store is valid yet
         HIPCHK(hipMemsetAsync(t + B, 0, B * sizeof(int), h->stream));
         h->s.warm = w;
@@ -991,13 +1032,7 @@ dekf_status dekf_set_warm_start(dekf_handle h, int on) {
         h->sp[0] = h->s;
         h->sp[1] = h->s;  // (not pipelined)
     }
-    h->c.warm = on;
-    // a full-window kernel whose register budget left the warm start's code out: its twin carries it
-    if (const SolveKernel* k = h->solve_entry_full; k && k->warm_twin) {
-        const bool pol = h->c.polish != 0;
-        h->solve_kernel_full = on ? (pol ? k->fn_warm_pol : k->fn_warm) : (pol ? k->fn_pol : k->fn);
-        h->solve_name_full = on ? (pol ? k->name_warm_pol : k->name_warm) : (pol ? k->name_pol : k->name);
-    }
+    h->c.warm = on;  // (a full-window kernel whose register budget left the warm start's code out: solve_twin picks the twin that carries it)
     return DEKF_OK;
 }
 
@@ -1009,10 +1044,8 @@ dekf_status dekf_get_warm_status(dekf_handle h, int* warm, dekf_mem where) {
         else HIPCHK(hipMemsetAsync(warm, 0, n, h->stream));
         return DEKF_OK;
     }
-    dekf_status st;
-    if ((st = fetch(h, warm, h->s.warm_used, n, where))) return st;
-    if (where == DEKF_HOST) HIPCHK(hipStreamSynchronize(h->stream));
-    return DEKF_OK;
+    TRY(fetch(h, warm, h->s.warm_used, n, where));
+    return host_sync(h, where);
 }
 
 dekf_status dekf_set_solver(dekf_handle h, int solver) {
@@ -1028,12 +1061,7 @@ dekf_status dekf_set_solver(dekf_handle h, int solver) {
         const DirectKernel* k = direct_kernel(h->c.L, h->c.ft, h->c.N);
         if (!k) return fail(DEKF_ERR_INVALID, "no direct solve kernel for this shape");
         HIPCHK(hipSetDevice(h->device));
-        if (!h->mhe_cov) {
-            double* cv = nullptr;
-            HIPCHK(hipMalloc(&cv, (size_t)h->c.B * h->c.ns * h->c.ns * sizeof(double)));
-            h->blocks.push_back(cv);
-            h->mhe_cov = cv;
-        }
+        if (!h->mhe_cov) TRY(dev_alloc(h, (size_t)h->c.B * h->c.ns * h->c.ns * sizeof(double), &h->mhe_cov));
         h->direct = k;
         h->lds_direct = (size_t)DirectScratch::len(h->c.ns) * sizeof(double);
     }
@@ -1052,11 +1080,8 @@ dekf_status dekf_set_smoother(dekf_handle h, int on) {
     if (on && !h->win.x) {
         HIPCHK(hipSetDevice(h->device));
         const size_t B = (size_t)h->c.B, N = (size_t)h->c.N, ns = (size_t)h->c.ns;
-        double* st = nullptr;  // x | cov | t1 in one block
-        HIPCHK(hipMalloc(&st, B * (N * ns + (2 * N - 1) * ns * ns) * sizeof(double)));
-        h->blocks.push_back(st);
-        h->win.x = st;
-        h->win.cov = st + B * N * ns;
+        TRY(dev_alloc(h, B * (N * ns + (2 * N - 1) * ns * ns) * sizeof(double), &h->win.x));  // x | cov | t1 in one block
+        h->win.cov = h->win.x + B * N * ns;
         h->win.t1 = h->win.cov + B * N * ns * ns;
     }
     h->smoother = on != 0;
@@ -1073,10 +1098,7 @@ dekf_status dekf_set_window_cross(dekf_handle h, int on) {
     if (on && !h->cross_st.newest) {
         HIPCHK(hipSetDevice(h->device));
         const size_t B = (size_t)h->c.B, N = (size_t)h->c.N, ns = (size_t)h->c.ns;
-        double* st = nullptr;  // (the lag-one blocks take the smoother's t1 store)
-        HIPCHK(hipMalloc(&st, B * N * ns * ns * sizeof(double)));
-        h->blocks.push_back(st);
-        h->cross_st.newest = st;
+        TRY(dev_alloc(h, B * N * ns * ns * sizeof(double), &h->cross_st.newest));  // (the lag-one blocks take the smoother's t1 store)
     }
     h->cross = on != 0;
     h->win_steps = 0;
@@ -1087,21 +1109,12 @@ dekf_status dekf_get_window(dekf_handle h, int* steps, double* x_win, double* co
     if (!h) return fail(DEKF_ERR_INVALID, "null handle");
     if (!h->smoother) return fail(DEKF_ERR_INVALID, "dekf_get_window needs a smoothing handle (dekf_set_smoother(h, 1))");
     if (!h->win_steps) return fail(DEKF_ERR_ORDER, "dekf_get_window before the first update (since dekf_create or dekf_reset)");
-    const size_t N = (size_t)h->c.N, ns = (size_t)h->c.ns, K = (size_t)h->win_steps;
+    const size_t B = (size_t)h->c.B, N = (size_t)h->c.N, ns = (size_t)h->c.ns, K = (size_t)h->win_steps;
     if (steps) *steps = h->win_steps;
     // the K written entries of every instance: [B][N][...] with a pitch of N entries on both sides
-    const hipMemcpyKind kind = where == DEKF_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    const size_t B = (size_t)h->c.B;
-    if (K == N) {  // full windows: one contiguous copy each
-        dekf_status st;
-        if ((st = fetch(h, x_win, h->win.x, B * N * ns * 8, where))) return st;
-        if ((st = fetch(h, cov_win, h->win.cov, B * N * ns * ns * 8, where))) return st;
-    } else {
-        if (x_win) HIPCHK(hipMemcpy2DAsync(x_win, N * ns * 8, h->win.x, N * ns * 8, K * ns * 8, B, kind, h->stream));
-        if (cov_win) HIPCHK(hipMemcpy2DAsync(cov_win, N * ns * ns * 8, h->win.cov, N * ns * ns * 8, K * ns * ns * 8, B, kind, h->stream));
-    }
-    if (where == DEKF_HOST && (x_win || cov_win)) HIPCHK(hipStreamSynchronize(h->stream));
-    return DEKF_OK;
+    TRY(fetch_rows(h, x_win, h->win.x, N * ns * 8, K * ns * 8, B, where));
+    TRY(fetch_rows(h, cov_win, h->win.cov, N * ns * ns * 8, K * ns * ns * 8, B, where));
+    return x_win || cov_win ? host_sync(h, where) : DEKF_OK;
 }
 
 dekf_status dekf_get_window_cross(dekf_handle h, int* steps, double* cov_lag1, double* cov_newest, dekf_mem where) {
@@ -1111,35 +1124,23 @@ dekf_status dekf_get_window_cross(dekf_handle h, int* steps, double* cov_lag1, d
     const size_t B = (size_t)h->c.B, N = (size_t)h->c.N, n2 = (size_t)h->c.ns * h->c.ns, K = (size_t)h->win_steps;
     if (steps) *steps = h->win_steps;
     // the K - 1 and K written entries of every instance: [B][N - 1][ns^2] and [B][N][ns^2], the pitch the same on both sides
-    const hipMemcpyKind kind = where == DEKF_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (K == N) {  // full windows: one contiguous copy each
-        dekf_status st;
-        if ((st = fetch(h, cov_lag1, h->win.t1, B * (N - 1) * n2 * 8, where))) return st;
-        if ((st = fetch(h, cov_newest, h->cross_st.newest, B * N * n2 * 8, where))) return st;
-    } else {
-        if (cov_lag1) HIPCHK(hipMemcpy2DAsync(cov_lag1, (N - 1) * n2 * 8, h->win.t1, (N - 1) * n2 * 8, (K - 1) * n2 * 8, B, kind, h->stream));
-        if (cov_newest) HIPCHK(hipMemcpy2DAsync(cov_newest, N * n2 * 8, h->cross_st.newest, N * n2 * 8, K * n2 * 8, B, kind, h->stream));
-    }
-    if (where == DEKF_HOST && (cov_lag1 || cov_newest)) HIPCHK(hipStreamSynchronize(h->stream));
-    return DEKF_OK;
+    TRY(fetch_rows(h, cov_lag1, h->win.t1, (N - 1) * n2 * 8, (K - 1) * n2 * 8, B, where));
+    TRY(fetch_rows(h, cov_newest, h->cross_st.newest, N * n2 * 8, K * n2 * 8, B, where));
+    return cov_lag1 || cov_newest ? host_sync(h, where) : DEKF_OK;
 }
 
 dekf_status dekf_get_mhe_cov(dekf_handle h, double* cov, dekf_mem where) {
     if (!h || !cov) return fail(DEKF_ERR_INVALID, "null argument");
     if (h->solver != DEKF_SOLVER_DIRECT) return fail(DEKF_ERR_INVALID, "dekf_get_mhe_cov needs a direct handle (dekf_set_solver(h, DEKF_SOLVER_DIRECT))");
     if (!h->mhe_cov_valid) return fail(DEKF_ERR_ORDER, "dekf_get_mhe_cov before the first update (since dekf_create or dekf_reset)");
-    dekf_status st = fetch(h, cov, h->mhe_cov, (size_t)h->c.ns * h->c.ns * h->c.B * 8, where);
-    if (st) return st;
-    if (where == DEKF_HOST) HIPCHK(hipStreamSynchronize(h->stream));
-    return DEKF_OK;
+    TRY(fetch(h, cov, h->mhe_cov, (size_t)h->c.ns * h->c.ns * h->c.B * 8, where));
+    return host_sync(h, where);
 }
 
 dekf_status dekf_get_kf_cov(dekf_handle h, double* cov, dekf_mem where) {
     if (!h || !cov) return fail(DEKF_ERR_INVALID, "null argument");
-    dekf_status st = fetch(h, cov, h->s.kf_C, (size_t)h->c.ns * h->c.ns * h->c.B * 8, where);
-    if (st) return st;
-    if (where == DEKF_HOST) HIPCHK(hipStreamSynchronize(h->stream));
-    return DEKF_OK;
+    TRY(fetch(h, cov, h->s.kf_C, (size_t)h->c.ns * h->c.ns * h->c.B * 8, where));
+    return host_sync(h, where);
 }
 
 dekf_status dekf_timing_enable(dekf_handle h, int on) {
@@ -1185,7 +1186,7 @@ dekf_status dekf_launch_info(dekf_handle h, int* solve_workgroups, int* compute_
     if (!h) return fail(DEKF_ERR_INVALID, "null handle");
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, h->device));
-    if (solve_workgroups) *solve_workgroups = h->solver == DEKF_SOLVER_DIRECT ? h->c.B : (h->solve_kernel_full ? h->solve_grid_full : h->solve_grid);
+    if (solve_workgroups) *solve_workgroups = solve_launch(h, h->c.N).grid;  // (the full-window kernel's where the handle has one)
     if (compute_units) *compute_units = prop.multiProcessorCount;
     if (clock_hz) *clock_hz = (double)prop.clockRate * 1e3;
     return DEKF_OK;
@@ -1193,19 +1194,16 @@ dekf_status dekf_launch_info(dekf_handle h, int* solve_workgroups, int* compute_
 
 const char* dekf_solve_kernel_name(dekf_handle h, int full_window) {
     if (!h || h->c.est_type != 0) return nullptr;
-    if (h->solver == DEKF_SOLVER_DIRECT && h->epochs) return h->cross ? h->direct->name_cross_ep : h->smoother ? h->direct->name_smooth_ep : h->direct->name_ep;
-    if (h->solver == DEKF_SOLVER_DIRECT) return h->cross ? h->direct->name_cross : h->smoother ? h->direct->name_smooth : h->direct->name;
-    return (full_window && h->solve_kernel_full) ? h->solve_name_full : h->solve_name;
+    return solve_launch(h, full_window ? h->c.N : h->c.N - 1).name;
 }
 
 // not part of include/dekf.h: section cycles [B][DEKF_PROF_SLOTS] of the last solve; all zero unless this
 // library was built with -DDEKF_PROFILE (libdekf_prof.so, tools/profile_sections.py)
 dekf_status dekf_debug_sections(dekf_handle h, double* out_host) {
     if (!h || !out_host) return fail(DEKF_ERR_INVALID, "null argument");
-    { dekf_status st = await_results(h); if (st) return st; }
-    HIPCHK(hipMemcpyAsync(out_host, h->sp[h->last_par].prof, DEKF_PROF_SLOTS * (size_t)h->c.B * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return DEKF_OK;
+    TRY(await_results(h));
+    TRY(fetch(h, out_host, h->sp[h->last_par].prof, DEKF_PROF_SLOTS * (size_t)h->c.B * 8, DEKF_HOST));
+    return host_sync(h, DEKF_HOST);
 }
 
 #ifdef DEKF_BOUNDS

@@ -338,24 +338,7 @@ __global__ void k_fold_epochs(int* c0, int B, int count_old, int count_new, int 
 __global__ void k_reset_state(DevCfg c, DevState s) {
     int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= c.B) return;
-    size_t B = (size_t)c.B;
-    for (int i = 0; i < 4; ++i) { s.ekf_q[i * B + b] = c.ekf_q0[i]; s.quat[4 * (size_t)b + i] = c.ekf_q0[i]; }
-    for (int i = 0; i < 16; ++i) s.ekf_P[i * B + b] = (i % 5 == 0) ? c.ekf_P0[i / 5] : 0.0;
-    s.vo_flag[b] = 0;
-    s.ekf_vo_flag[b] = 0;
-    s.wp_count[b] = 0;
-    for (int i = 0; i < 3; ++i) s.p_vo[3 * (size_t)b + i] = 0.0;
-    for (int i = 0; i < c.ns; ++i) s.x_mhe[(size_t)c.ns * b + i] = 0.0;
-    for (int i = 0; i < 3; ++i) s.v_b[3 * (size_t)b + i] = 0.0;
-    s.status[b] = DEKF_SOLVE_NONE;
-    s.iters[b] = 0;
-    s.rho_updates[b] = 0;
-    s.polish_status[b] = 0;
-    s.pri_res[b] = 0.0;
-    s.dua_res[b] = 0.0;
-    s.vo_ins_idx[b] = 0;
-    s.vo_ins_dtime[b] = 0;
-    s.marg_tag[b] = -1;
+    reset_state_of(c, s, b);  // (mhe_epoch_core.h: what dekf_reset_instances does to one instance)
     if (s.warm_tag) {  // (dekf_reset: no solve starts warm from before it)
         s.warm_tag[b] = -1;
         s.warm_used[b] = 0;

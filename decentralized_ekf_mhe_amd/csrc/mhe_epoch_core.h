@@ -21,9 +21,8 @@
 namespace dekf {
 
 // What k_reset_state does for instance b (one lane per instance): EKF state and covariance at their initial values, VO latches, way
-// points and the p_vo accumulator cleared, outputs and solver info zeroed, no arrival cost computed ahead.
-// (k_reset_state keeps its own lines: called from here it would be another code object, and no kernel from before this file changes.
-// A direct handle has no warm store, so its tags are not part of this.)
+// points and the p_vo accumulator cleared, outputs and solver info zeroed, no arrival cost computed ahead.  (k_reset_state adds the
+// warm store's tags; a direct handle has no warm store.)
 DEKF_FN void reset_state_of(const DevCfg& c, const DevState& s, int b) {
     const size_t B = (size_t)c.B;
     for (int i = 0; i < 4; ++i) { s.ekf_q[i * B + b] = c.ekf_q0[i]; s.quat[4 * (size_t)b + i] = c.ekf_q0[i]; }
