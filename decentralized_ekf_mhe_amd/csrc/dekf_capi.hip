@@ -14,6 +14,7 @@
 #include "mhe_assemble_core.h"
 #include "mhe_direct_core.h"
 #include "mhe_epoch_core.h"
+#include "mhe_params_core.h"
 #include "mhe_solve_core.h"
 
 using namespace dekf;
@@ -37,7 +38,10 @@ __global__ void k_mhe_marginalize_early(DevCfg c, DevState s, int T);
     __global__ void NAME##_smooth_cross(DevCfg c, DevState s, int kstart, int K, double* cov, DirectWindow win, DirectCross cross); \
     __global__ void NAME##_ep(DevCfg c, DevState s, int T, double* cov, const int* t0); \
     __global__ void NAME##_smooth_ep(DevCfg c, DevState s, int T, double* cov, DirectWindow win, const int* t0); \
-    __global__ void NAME##_smooth_cross_ep(DevCfg c, DevState s, int T, double* cov, DirectWindow win, DirectCross cross, const int* t0);
+    __global__ void NAME##_smooth_cross_ep(DevCfg c, DevState s, int T, double* cov, DirectWindow win, DirectCross cross, const int* t0); \
+    __global__ void NAME##_pp(DevState s, int T, double* cov, const int* t0, const DevCfg* pc); \
+    __global__ void NAME##_smooth_pp(DevState s, int T, double* cov, DirectWindow win, const int* t0, const DevCfg* pc); \
+    __global__ void NAME##_smooth_cross_pp(DevState s, int T, double* cov, DirectWindow win, DirectCross cross, const int* t0, const DevCfg* pc);
 #include "direct_kernels.def"
 __global__ void k_gap();
 __global__ void k_kf_initialize(DevCfg c, DevState s);
@@ -51,6 +55,13 @@ __global__ void k_fold_epochs(int* c0, int B, int count_old, int count_new, int 
 __global__ void k_ekf_tick_ep(DevCfg c, DevState s, int count, const int* c0);
 __global__ void k_mhe_assemble_ep(DevCfg c, DevState s, int T, int pushes, const int* t0);
 __global__ void k_mhe_marginalize_early_ep(DevCfg c, DevState s, int T, const int* t0);
+// noise parameters per instance (mhe_params_core.h)
+__global__ void k_ekf_tick_pp(DevCfg c, DevState s, int count, const int* c0, const double* pe);
+__global__ void k_mhe_assemble_pp(DevState s, int T, int pushes, const int* t0, const DevCfg* pc);
+__global__ void k_mhe_marginalize_early_pp(DevState s, int T, const int* t0, const DevCfg* pc);
+__global__ void k_reset_instances_pp(DevCfg c, DevState s, const int* mask, double* cov, int* t0, int* c0, int next_T, int ekf_count, const double* pe);
+__global__ void k_reset_state_pp(DevCfg c, DevState s, const double* pe);
+__global__ void k_ekf_init_pp(DevCfg c, DevState s, const int* mask, const double* pe);
 __global__ void k_ekf_cov_out(DevCfg c, DevState s, double* out);
 __global__ void k_latch4(LatchCopy4 a);
 __global__ void k_go1_leg_odometry(DevCfg c, DevState s, const double* jp, const double* jv, const double* force,
@@ -111,6 +122,16 @@ struct dekf_handle_s {
     std::vector<int> t0_host;
     int min_t0 = 0;
     bool epochs = false;
+    // dekf_set_instance_params: the noise constants of every instance of a direct handle (mhe_params_core.h).  pp_mhe [B] DevCfg
+    // and pp_ekf [PpEkf::len][B] on the device, allocated by the first call that sets a table; inst_prm: the handle's parameters with
+    // every instance's noise fields (dekf_get_instance_params).  pp: the handle has a table: it launches the *_pp kernels, which are
+    // the epoch kernels with the table as one more argument, so the epoch arrays exist (all 0 unless `epochs`).  ekf_ticked: a
+    // dekf_ekf_step since the last dekf_update / dekf_initialize / dekf_reset: the instances at local tick -1 are no longer at EKF tick 0
+    DevCfg* pp_mhe = nullptr;
+    double* pp_ekf = nullptr;
+    std::vector<dekf_params> inst_prm;
+    bool pp = false;
+    bool ekf_ticked = false;
     size_t lds_solve = 0, lds_asm = 0, lds_kf = 0;
     int ekf_count = 0, pushes = 0, next_T = 0;
     bool initialized = false;
@@ -216,9 +237,12 @@ typedef void (*DirectCrossFn)(DevCfg, DevState, int, int, double*, DirectWindow,
 typedef void (*DirectEpochFn)(DevCfg, DevState, int, double*, const int*);
 typedef void (*DirectSmoothEpochFn)(DevCfg, DevState, int, double*, DirectWindow, const int*);
 typedef void (*DirectCrossEpochFn)(DevCfg, DevState, int, double*, DirectWindow, DirectCross, const int*);
-// the six kernels of a row: the direct solve, its smoothing twin (dekf_set_smoother), the twin with the window cross-covariances
-// (dekf_set_window_cross), and the epoch twins of the three (dekf_reset_instances)
-enum DirectVariant { plain, smooth, cross, plain_ep, smooth_ep, cross_ep };
+typedef void (*DirectParamFn)(DevState, int, double*, const int*, const DevCfg*);
+typedef void (*DirectSmoothParamFn)(DevState, int, double*, DirectWindow, const int*, const DevCfg*);
+typedef void (*DirectCrossParamFn)(DevState, int, double*, DirectWindow, DirectCross, const int*, const DevCfg*);
+// the nine kernels of a row: the direct solve, its smoothing twin (dekf_set_smoother), the twin with the window cross-covariances
+// (dekf_set_window_cross), the epoch twins of the three (dekf_reset_instances) and the parameter twins of those (dekf_set_instance_params)
+enum DirectVariant { plain, smooth, cross, plain_ep, smooth_ep, cross_ep, plain_pp, smooth_pp, cross_pp };
 struct DirectKernel {
     int legs, ft, nfix;  // direct_solve_t's L and FT; the horizon the row is meant for (0: any)
     DirectFn fn;
@@ -227,11 +251,16 @@ struct DirectKernel {
     DirectEpochFn fn_ep;
     DirectSmoothEpochFn fn_smooth_ep;
     DirectCrossEpochFn fn_cross_ep;
-    const char* name[6];  // by DirectVariant
+    DirectParamFn fn_pp;
+    DirectSmoothParamFn fn_smooth_pp;
+    DirectCrossParamFn fn_cross_pp;
+    const char* name[9];  // by DirectVariant
 };
 #define DEKF_DIRECT_KERNEL(NAME, L, FT, NFIX)                                                                                \
     {L, FT, NFIX, NAME, NAME##_smooth, NAME##_smooth_cross, NAME##_ep, NAME##_smooth_ep, NAME##_smooth_cross_ep,              \
-     {#NAME, #NAME "_smooth", #NAME "_smooth_cross", #NAME "_ep", #NAME "_smooth_ep", #NAME "_smooth_cross_ep"}},
+     NAME##_pp, NAME##_smooth_pp, NAME##_smooth_cross_pp,                                                                    \
+     {#NAME, #NAME "_smooth", #NAME "_smooth_cross", #NAME "_ep", #NAME "_smooth_ep", #NAME "_smooth_cross_ep",              \
+      #NAME "_pp", #NAME "_smooth_pp", #NAME "_smooth_cross_pp"}},
 const DirectKernel direct_kernels[] = {
 #include "direct_kernels.def"
 };
@@ -248,10 +277,11 @@ const DirectKernel* direct_kernel(int L, int ft, int N) {
 }
 
 // the kernel of its row that a direct handle launches: the smoother and cross settings pick the twin, and a handle that has restarted
-// an instance (epochs) launches the epoch twin of that one, which finds every instance's window from the step
+// an instance (epochs) launches the epoch twin of that one, which finds every instance's window from the step; a handle with a
+// parameter table (pp) the parameter twin of the epoch twin, with or without a restarted instance
 DirectVariant direct_variant(const dekf_handle_s* h) {
     const int v = !h->smoother ? plain : (h->cross ? cross : smooth);
-    return (DirectVariant)(h->epochs ? v + plain_ep : v);
+    return (DirectVariant)(h->pp ? v + plain_pp : (h->epochs ? v + plain_ep : v));
 }
 
 // The solve launch of a step with a window of K steps: what dekf_update launches, dekf_solve_kernel_name names and dekf_launch_info
@@ -410,6 +440,20 @@ dekf_status quiesce(dekf_handle h) {
     return DEKF_OK;
 }
 
+// the epoch arrays of a direct handle (t0 | c0 in one block, all 0), allocated by the first call that needs them
+dekf_status ensure_epochs(dekf_handle h) {
+    if (h->ep_t0) return DEKF_OK;
+    const size_t B = (size_t)h->c.B;
+    int* e = nullptr;
+    TRY(dev_alloc(h, 2 * B * sizeof(int), &e));
+    HIPCHK(hipMemsetAsync(e, 0, 2 * B * sizeof(int), h->stream));
+    h->ep_t0 = e;
+    h->ep_c0 = e + B;
+    h->t0_host.assign(B, 0);
+    h->min_t0 = 0;
+    return DEKF_OK;
+}
+
 struct Timed {  // brackets one launch with events when timing is on
     dekf_handle h;
     int cls;
@@ -453,7 +497,8 @@ dekf_status assemble_step(dekf_handle h, const MheStep& st) {
     if (h->early_pending) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_early_done, 0)); h->early_pending = false; }
     {
         Timed t(h, 1);
-        if (h->epochs) k_mhe_assemble_ep<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->c, st.sp, st.T, h->pushes, h->ep_t0);
+        if (h->pp) k_mhe_assemble_pp<<<h->c.B, 64, h->lds_asm, h->stream>>>(st.sp, st.T, h->pushes, h->ep_t0, h->pp_mhe);
+        else if (h->epochs) k_mhe_assemble_ep<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->c, st.sp, st.T, h->pushes, h->ep_t0);
         else k_mhe_assemble<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->c, st.sp, st.T, h->pushes);
     }
     HIPCHK(hipGetLastError());
@@ -473,6 +518,10 @@ void launch_solve(dekf_handle h, const SolveLaunch& l, const DevState& sp, int T
     case plain_ep: d.fn_ep<<<l.grid, l.threads, l.lds, ss>>>(h->c, sp, T, h->mhe_cov, h->ep_t0); break;
     case smooth_ep: d.fn_smooth_ep<<<l.grid, l.threads, l.lds, ss>>>(h->c, sp, T, h->mhe_cov, h->win, h->ep_t0); break;
     case cross_ep: d.fn_cross_ep<<<l.grid, l.threads, l.lds, ss>>>(h->c, sp, T, h->mhe_cov, h->win, h->cross_st, h->ep_t0); break;
+    // (a direct handle with a parameter table: the parameter twins, the epoch twins with every instance's row of the table)
+    case plain_pp: d.fn_pp<<<l.grid, l.threads, l.lds, ss>>>(sp, T, h->mhe_cov, h->ep_t0, h->pp_mhe); break;
+    case smooth_pp: d.fn_smooth_pp<<<l.grid, l.threads, l.lds, ss>>>(sp, T, h->mhe_cov, h->win, h->ep_t0, h->pp_mhe); break;
+    case cross_pp: d.fn_cross_pp<<<l.grid, l.threads, l.lds, ss>>>(sp, T, h->mhe_cov, h->win, h->cross_st, h->ep_t0, h->pp_mhe); break;
     }
 }
 
@@ -522,7 +571,8 @@ dekf_status solve_step(dekf_handle h, const MheStep& st) {
 dekf_status marginalize_next_early(dekf_handle h, int T) {
     HIPCHK(hipStreamWaitEvent(h->early_stream, h->ev_asm_done, 0));
     HIPCHK(hipEventRecord(h->ev_early_mark, h->early_stream));  // (as before a pipelined solve launch: see there)
-    if (h->epochs) k_mhe_marginalize_early_ep<<<h->c.B, 64, h->lds_asm, h->early_stream>>>(h->c, h->s, T + 1, h->ep_t0);
+    if (h->pp) k_mhe_marginalize_early_pp<<<h->c.B, 64, h->lds_asm, h->early_stream>>>(h->s, T + 1, h->ep_t0, h->pp_mhe);
+    else if (h->epochs) k_mhe_marginalize_early_ep<<<h->c.B, 64, h->lds_asm, h->early_stream>>>(h->c, h->s, T + 1, h->ep_t0);
     else k_mhe_marginalize_early<<<h->c.B, 64, h->lds_asm, h->early_stream>>>(h->c, h->s, T + 1);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev_early_done, h->early_stream));
@@ -731,11 +781,13 @@ dekf_status dekf_reset(dekf_handle h) {
     TRY(quiesce(h));
     for (int i = 0; i < DEKF_SNAP_SETS; ++i) h->snap_busy[i] = false;  // (every solve is behind the events just waited for)
     for (int i = 0; i < (h->pipelined ? 2 : 1); ++i) {
-        k_reset_state<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->sp[i]);
+        if (h->pp) k_reset_state_pp<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->sp[i], h->pp_ekf);  // (the table survives)
+        else k_reset_state<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->sp[i]);
         HIPCHK(hipGetLastError());
     }
     h->last_par = h->ekf_count = h->pushes = h->next_T = 0;
     h->initialized = false;
+    h->ekf_ticked = false;
     h->mhe_cov_valid = false;  // (the solver, smoother and cross settings survive)
     h->win_steps = 0;
     if (h->ep_t0) {  // every epoch: the handle launches the kernels of a handle that never restarted an instance again
@@ -771,21 +823,15 @@ dekf_status dekf_reset_instances(dekf_handle h, const int* mask, dekf_mem where)
     }
     if (!any) return DEKF_OK;  // nothing changes, the kernels the handle launches included
     TRY(quiesce(h));  // (what dekf_reset waits for)
-    if (!h->ep_t0) {
-        int* e = nullptr;  // t0 | c0 in one block
-        TRY(dev_alloc(h, 2 * B * sizeof(int), &e));
-        HIPCHK(hipMemsetAsync(e, 0, 2 * B * sizeof(int), h->stream));
-        h->ep_t0 = e;
-        h->ep_c0 = e + B;
-        h->t0_host.assign(B, 0);
-        h->min_t0 = 0;
-    }
+    TRY(ensure_epochs(h));
     const int* dmask = where == DEKF_HOST ? m.data() : mask;
     if (where == DEKF_HOST) {
         TRY(ensure_stage(h, B * sizeof(int)));
         TRY(stage_in(h, 0, &dmask, B));
     }
-    k_reset_instances<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->s, dmask, h->mhe_cov, h->ep_t0, h->ep_c0, h->next_T, h->ekf_count);
+    if (h->pp)  // (every instance's own initial EKF state)
+        k_reset_instances_pp<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->s, dmask, h->mhe_cov, h->ep_t0, h->ep_c0, h->next_T, h->ekf_count, h->pp_ekf);
+    else k_reset_instances<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->s, dmask, h->mhe_cov, h->ep_t0, h->ep_c0, h->next_T, h->ekf_count);
     HIPCHK(hipGetLastError());
     if (where == DEKF_HOST) HIPCHK(hipStreamSynchronize(h->stream));  // (m, a local, is the source of the copy)
     h->min_t0 = h->next_T;
@@ -811,6 +857,89 @@ dekf_status dekf_get_instance_ticks(dekf_handle h, int* ticks, dekf_mem where) {
         HIPCHK(hipMemcpyAsync(ticks, t.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));  // (t is a local)
     }
+    return DEKF_OK;
+}
+
+dekf_status dekf_set_instance_params(dekf_handle h, const dekf_params* sets, int nsets, const int* set_of) {
+    if (!h) return fail(DEKF_ERR_INVALID, "null handle");
+    if (h->c.est_type != 0) return fail(DEKF_ERR_INVALID, "dekf_set_instance_params needs a direct MHE handle: this is a KF handle (est_type 1)");
+    if (h->pipelined) return fail(DEKF_ERR_INVALID, "dekf_set_instance_params cannot be combined with solve_pipeline = 1");
+    if (h->solver != DEKF_SOLVER_DIRECT) return fail(DEKF_ERR_INVALID, "dekf_set_instance_params needs a direct handle (dekf_set_solver(h, DEKF_SOLVER_DIRECT))");
+    if (nsets < 0) return fail(DEKF_ERR_INVALID, "dekf_set_instance_params: nsets must be >= 0");
+    if (nsets == 0 ? (sets || set_of) : (!sets || !set_of))
+        return fail(DEKF_ERR_INVALID, "dekf_set_instance_params: sets and set_of must both be given (nsets > 0) or both be NULL (nsets = 0)");
+    const size_t B = (size_t)h->c.B;
+    const bool fresh = !h->initialized && h->ekf_count == 0;  // before the first tick since dekf_create / dekf_reset
+    if (nsets == 0) {  // drop the table: the handle's own constants for every instance, and its former kernels
+        if (!h->pp) return DEKF_OK;
+        if (!fresh) return fail(DEKF_ERR_ORDER, "dekf_set_instance_params: the table is dropped before the first tick or right after dekf_reset");
+        HIPCHK(hipSetDevice(h->device));
+        TRY(quiesce(h));
+        h->pp = false;
+        h->inst_prm.clear();
+        k_reset_state<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->s);  // (the EKF state at the handle's initial values)
+        HIPCHK(hipGetLastError());
+        return DEKF_OK;
+    }
+    // everything is checked before anything is applied
+    for (int k = 0; k < nsets; ++k) {
+        if (!same_but_noise(sets[k], h->prm))
+            return fail(DEKF_ERR_INVALID, "dekf_set_instance_params: a set differs from the handle's parameters in a field that is not a noise field");
+        if (const char* msg = check_noise(sets[k])) return fail(DEKF_ERR_INVALID, msg);
+    }
+    const int T = h->next_T - 1;
+    bool any = false;
+    for (size_t b = 0; b < B; ++b) {
+        if (set_of[b] < -1 || set_of[b] >= nsets) return fail(DEKF_ERR_INVALID, "dekf_set_instance_params: set_of entries must lie in -1 .. nsets - 1");
+        any = any || set_of[b] >= 0;
+    }
+    if (!fresh)
+        for (size_t b = 0; b < B; ++b) {
+            if (set_of[b] < 0) continue;
+            // only an instance that dekf_reset_instances has restarted and that has seen neither an update nor an EKF tick since
+            const bool restarted = h->initialized && h->epochs && T - h->t0_host[b] == -1 && !h->ekf_ticked;
+            if (!restarted)
+                return fail(DEKF_ERR_ORDER, "dekf_set_instance_params: an instance takes a set before its first tick only (before the first "
+                                            "dekf_ekf_step, right after dekf_reset, or right after dekf_reset_instances restarted it)");
+        }
+    HIPCHK(hipSetDevice(h->device));
+    TRY(quiesce(h));  // (the arrival cost computed ahead reads the table)
+    TRY(ensure_epochs(h));
+    if (!h->pp_mhe) {
+        TRY(dev_alloc(h, B * sizeof(DevCfg), &h->pp_mhe));
+        TRY(dev_alloc(h, B * PpEkf::len * sizeof(double), &h->pp_ekf));
+    }
+    if (!h->pp) h->inst_prm.assign(B, h->prm);  // (a new table: every instance on the handle's own set)
+    for (size_t b = 0; b < B; ++b)
+        if (set_of[b] >= 0) h->inst_prm[b] = with_noise_of(h->prm, sets[set_of[b]]);
+    // both tables are written whole from the host's copy (the entries of untouched instances with the values they hold): the handle's
+    // DevCfg with the constants fill_cfg derives for a handle created with the instance's set
+    std::vector<DevCfg> tm(B, h->c);
+    std::vector<double> te(B * PpEkf::len);
+    std::vector<int> mask(B);
+    for (size_t b = 0; b < B; ++b) {
+        fill_noise(h->inst_prm[b], tm[b]);
+        pp_pack_ekf(tm[b], te.data(), B, b);
+        mask[b] = set_of[b] >= 0;
+    }
+    HIPCHK(hipMemcpyAsync(h->pp_mhe, tm.data(), tm.size() * sizeof(DevCfg), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->pp_ekf, te.data(), te.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (any) {  // the EKF state of the instances that took a set: their set's initial quaternion and covariance
+        const int* dmask = mask.data();
+        TRY(ensure_stage(h, B * sizeof(int)));
+        TRY(stage_in(h, 0, &dmask, B));
+        k_ekf_init_pp<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->s, dmask, h->pp_ekf);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));  // (the sources of the copies are locals)
+    h->pp = true;
+    return DEKF_OK;
+}
+
+dekf_status dekf_get_instance_params(dekf_handle h, int b, dekf_params* out) {
+    if (!h || !out) return fail(DEKF_ERR_INVALID, "null argument");
+    if (b < 0 || b >= h->c.B) return fail(DEKF_ERR_INVALID, "dekf_get_instance_params: instance out of range");
+    *out = h->pp ? h->inst_prm[(size_t)b] : h->prm;
     return DEKF_OK;
 }
 
@@ -898,11 +1027,13 @@ dekf_status dekf_ekf_step(dekf_handle h) {
     if (!h) return fail(DEKF_ERR_INVALID, "null handle");
     {
         Timed t(h, 0);
-        if (h->epochs) k_ekf_tick_ep<<<(h->c.B + 63) / 64, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count, h->ep_c0);
+        if (h->pp) k_ekf_tick_pp<<<(h->c.B + 63) / 64, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count, h->ep_c0, h->pp_ekf);
+        else if (h->epochs) k_ekf_tick_ep<<<(h->c.B + 63) / 64, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count, h->ep_c0);
         else k_ekf_tick<<<(h->c.B + 63) / 64, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count);
     }
     HIPCHK(hipGetLastError());
     h->ekf_count++;
+    h->ekf_ticked = true;
     // the kernel uses the count only modulo the ring depth and to know whether the ring is full: folded long before
     // the int overflows (a 500 Hz node reaches 2^31 ticks after 49 days)
     if (h->ekf_count >= (1 << 30)) {
@@ -922,7 +1053,9 @@ dekf_status dekf_initialize(dekf_handle h) {
     if (!h) return fail(DEKF_ERR_INVALID, "null handle");
     if (h->initialized) return fail(DEKF_ERR_ORDER, "dekf_initialize called twice without dekf_reset");
     if (h->c.est_type == 0) {
-        k_mhe_initialize<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->c, h->s);
+        // (a handle with a parameter table: the epoch path, whose step 0 is the initialise path on every instance's own prior)
+        if (h->pp) k_mhe_assemble_pp<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->s, 0, 0, h->ep_t0, h->pp_mhe);
+        else k_mhe_initialize<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->c, h->s);
         h->pushes = 1;
     } else {
         k_kf_initialize<<<h->c.B, 64, h->lds_kf, h->stream>>>(h->c, h->s);
@@ -931,6 +1064,7 @@ dekf_status dekf_initialize(dekf_handle h) {
     HIPCHK(hipGetLastError());
     h->last_par = 0;
     h->initialized = true;
+    h->ekf_ticked = false;
     h->next_T = 1;
     return DEKF_OK;
 }
@@ -952,6 +1086,7 @@ dekf_status dekf_update(dekf_handle h, int T) {
     HIPCHK(hipGetLastError());
     h->pushes++;
     h->next_T++;
+    h->ekf_ticked = false;
     return DEKF_OK;
 }
 
@@ -1055,6 +1190,8 @@ dekf_status dekf_set_solver(dekf_handle h, int solver) {
     if (h->c.est_type != 0) return fail(DEKF_ERR_INVALID, "the solver is an MHE setting: this is a KF handle (est_type 1)");
     if (h->pipelined) return fail(DEKF_ERR_INVALID, "dekf_set_solver cannot be combined with solve_pipeline = 1");
     if (h->initialized) return fail(DEKF_ERR_ORDER, "dekf_set_solver is allowed before dekf_initialize or right after dekf_reset");
+    if (solver == DEKF_SOLVER_ADMM && h->pp)
+        return fail(DEKF_ERR_INVALID, "the handle has a parameter table (dekf_set_instance_params): drop it first (nsets = 0)");
     if (solver == DEKF_SOLVER_DIRECT) {
         if (h->c.polish) return fail(DEKF_ERR_INVALID, "the direct solve cannot be combined with osqp.polish = 1");
         if (h->c.warm) return fail(DEKF_ERR_INVALID, "the direct solve cannot be combined with warm start (dekf_set_warm_start)");

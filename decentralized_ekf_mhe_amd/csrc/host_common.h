@@ -46,45 +46,12 @@ inline void default_params(dekf_params* p) {
     p->arrival_cost_form = 0; p->solve_pipeline = 0; p->solve_workgroups_per_cu = 0; p->polish_accept_osqp = 0;
 }
 
-// returns nullptr when ok, else a message
-inline const char* fill_cfg(const dekf_params& p, int B, DevCfg& c) {
-    if (B < 1) return "batch must be >= 1";
-    if (p.num_legs < 1 || p.num_legs > DEKF_MAX_LEGS) return "num_legs out of range";
-    if (p.joints_per_leg < 1 || p.joints_per_leg > DEKF_MAX_JOINTS) return "joints_per_leg out of range";
-    if (p.leg_odom_type != 0 && p.leg_odom_type != 1) return "leg_odom_type must be 0 (foot velocity) or 1 (foot position)";
-    if (p.est_type != 0 && p.est_type != 1) return "est_type must be 0 (MHE) or 1 (KF)";
-    if (p.N < 2 || p.N > 128) return "N out of range [2,128]";
-    if (p.rate < 1 || p.ekf_rate < 1) return "rate must be positive";
-    if (p.ekf_history < 4) return "ekf_history must be >= 4";
-    if (p.polish != 0 && p.polish != 1) return "osqp.polish must be 0 or 1";
-    if (p.polish && !(p.delta > 0)) return "osqp.delta must be positive when osqp.polish is on";
-    // the polishing solve runs as an ADMM step with 1 / rho = delta on the equality rows, and rho lives in [RHO_MIN, RHO_MAX] * 1e3:
-    // outside this range the device would silently solve a differently regularised system than OSQP does
-    if (p.polish && !(p.delta >= 1e-9 && p.delta <= 1e3)) return "osqp.delta must lie in [1e-9, 1e3] when osqp.polish is on";
-    if (p.polish_refine_iter < 0 || p.polish_refine_iter > 100) return "polish_refine_iter out of range [0,100]";
-    if (p.arrival_cost_form != 0 && p.arrival_cost_form != 1) return "arrival_cost_form must be 0 (reference form) or 1 (information form)";
-    if (p.solve_pipeline != 0 && p.solve_pipeline != 1) return "solve_pipeline must be 0 (in order) or 1 (consecutive steps overlap)";
-    if (p.solve_workgroups_per_cu < 0 || p.solve_workgroups_per_cu > 8) return "solve_workgroups_per_cu out of range [0,8]";
-    if (p.leg_odom_type == 1) {  // these become gains 1 / std^2 (DecentralEst.cpp:47-51): a zero would be an infinite weight
-        for (int i = 0; i < 3; ++i)
-            if (!(p.foot_slide_std[i] > 0) || !(p.foot_init_std[i] > 0) || !(p.foot_swing_std[i] > 0))
-                return "leg_odom_type 1 needs positive foot_slide_std, foot_init_std and foot_swing_std";
-    }
-    if (!(p.sigma > 0) || !(p.rho > 0) || !(p.alpha > 0 && p.alpha < 2)) return "rho/sigma/alpha out of range";
-    std::memset(&c, 0, sizeof(c));
-    c.B = B; c.L = p.num_legs; c.nj = p.joints_per_leg; c.N = p.N; c.nm = 3 * p.num_legs;
-    c.ft = p.leg_odom_type; c.ns = 9 + 3 * c.ft * c.L;
-    c.SV = 2 * c.ns + c.nm + 3; c.SC = c.nm + c.ns + 3;
-    // window records: N + 1 slots (the N of a window and the one the next step fills); one more when steps are pipelined, because
-    // the term construction of step T then runs while the solve of step T - 2 may still be reading its window (dekf_capi.hip)
-    c.ring = 4 * p.N + 1; c.wcap = p.N + 1 + ((p.solve_pipeline == 1 && p.est_type == 0) ? 1 : 0); c.rec = Rec::len(c.L, c.ft);
-    c.snap_len = c.ns * c.ns + c.ns + 4 * c.wcap;
-    c.est_type = p.est_type;
-    c.marg_info = p.leg_odom_type == 1 && p.arrival_cost_form == 1;
-    c.dt = 1.0 / (double)p.rate;
-    c.hdt2 = 0.5 * c.dt * c.dt;
-    c.gws_wt = 0;  // (dekf_create sets it once the placement of the factor is known)
-    c.inf_thr = OSQP_INFTY * MIN_SCALING;
+// The constants that the noise fields of p alone decide (with c.dt and c.nj, which fill_cfg has set): C_*, Q_*, Q_bias_dt2 and the EKF's
+// ekf_C*, ekf_P0, ekf_q0.  fill_cfg calls it for the handle's parameters and dekf_set_instance_params for every set, so a set yields
+// the doubles a handle created with it would hold.  The noise fields: p_init_std, v_init_std, foot_init_std, accel_bias_init_std,
+// p_process_std, accel_input_std, gyro_input_std, accel_bias_std, joint_position_std, joint_velocity_std, foot_slide_std,
+// foot_swing_std, vo_p_std, ekf_init_std, ekf_process_std, ekf_gravity_meas_std, ekf_vo_meas_std, ekf_quaternion_init.
+inline void fill_noise(const dekf_params& p, DevCfg& c) {
     auto sq = [](double v) { return v * v; };
     for (int i = 0; i < 3; ++i) {
         c.C_p[i] = sq(p.p_process_std[i]);
@@ -109,6 +76,85 @@ inline const char* fill_cfg(const dekf_params& p, int B, DevCfg& c) {
         c.ekf_Caccel[i] = sq(p.ekf_gravity_meas_std[i]);
     }
     for (int i = 0; i < c.nj; ++i) { c.C_enc_pos[i] = sq(p.joint_position_std[i]); c.C_enc_vel[i] = sq(p.joint_velocity_std[i]); }
+    for (int i = 0; i < 4; ++i) {
+        c.ekf_Cvo[i] = sq(p.ekf_vo_meas_std[i]);
+        c.ekf_P0[i] = sq(p.ekf_init_std[i]);
+        c.ekf_q0[i] = p.ekf_quaternion_init[i];
+    }
+}
+
+// the positivity fill_cfg asks of the foot stds (leg_odom_type 1: they become gains 1 / std^2, DecentralEst.cpp:47-51: a zero would
+// be an infinite weight); nullptr when ok
+inline const char* check_noise(const dekf_params& p) {
+    if (p.leg_odom_type == 1) {
+        for (int i = 0; i < 3; ++i)
+            if (!(p.foot_slide_std[i] > 0) || !(p.foot_init_std[i] > 0) || !(p.foot_swing_std[i] > 0))
+                return "leg_odom_type 1 needs positive foot_slide_std, foot_init_std and foot_swing_std";
+    }
+    return nullptr;
+}
+
+// p with the noise fields of `from` (see fill_noise): what dekf_get_instance_params hands out
+inline dekf_params with_noise_of(dekf_params p, const dekf_params& from) {
+#define DEKF_COPY_(F) std::memcpy(p.F, from.F, sizeof(p.F))
+    DEKF_COPY_(p_init_std); DEKF_COPY_(v_init_std); DEKF_COPY_(foot_init_std); DEKF_COPY_(accel_bias_init_std);
+    DEKF_COPY_(p_process_std); DEKF_COPY_(accel_input_std); DEKF_COPY_(gyro_input_std); DEKF_COPY_(accel_bias_std);
+    DEKF_COPY_(joint_position_std); DEKF_COPY_(joint_velocity_std); DEKF_COPY_(foot_slide_std); DEKF_COPY_(foot_swing_std);
+    DEKF_COPY_(vo_p_std); DEKF_COPY_(ekf_init_std); DEKF_COPY_(ekf_process_std); DEKF_COPY_(ekf_gravity_meas_std);
+    DEKF_COPY_(ekf_vo_meas_std); DEKF_COPY_(ekf_quaternion_init);
+#undef DEKF_COPY_
+    return p;
+}
+
+// every field that is NOT a noise field is the same in a and b (field by field: the struct has padding): structure, rates, N, the
+// osqp.* block, contact_effort_threshold, the IMU-to-body transform, the form switches and launch tuning
+inline bool same_but_noise(const dekf_params& a, const dekf_params& b) {
+#define DEKF_SAME_(F) (std::memcmp(&a.F, &b.F, sizeof(a.F)) == 0)
+    return DEKF_SAME_(quaternion_ib) && DEKF_SAME_(p_ib) && DEKF_SAME_(num_legs) && DEKF_SAME_(joints_per_leg) && DEKF_SAME_(leg_odom_type) &&
+           DEKF_SAME_(contact_effort_threshold) && DEKF_SAME_(rate) && DEKF_SAME_(N) && DEKF_SAME_(est_type) && DEKF_SAME_(rho) &&
+           DEKF_SAME_(alpha) && DEKF_SAME_(delta) && DEKF_SAME_(sigma) && DEKF_SAME_(verbose) && DEKF_SAME_(adapt_rho) && DEKF_SAME_(polish) &&
+           DEKF_SAME_(max_qp_iter) && DEKF_SAME_(rel_tol) && DEKF_SAME_(abs_tol) && DEKF_SAME_(prim_tol) && DEKF_SAME_(dual_tol) &&
+           DEKF_SAME_(time_limit) && DEKF_SAME_(scaling_iters) && DEKF_SAME_(check_termination) && DEKF_SAME_(adaptive_rho_interval) &&
+           DEKF_SAME_(adaptive_rho_tolerance) && DEKF_SAME_(ekf_rate) && DEKF_SAME_(ekf_history) && DEKF_SAME_(polish_refine_iter) &&
+           DEKF_SAME_(arrival_cost_form) && DEKF_SAME_(solve_pipeline) && DEKF_SAME_(solve_workgroups_per_cu) && DEKF_SAME_(polish_accept_osqp);
+#undef DEKF_SAME_
+}
+
+// returns nullptr when ok, else a message
+inline const char* fill_cfg(const dekf_params& p, int B, DevCfg& c) {
+    if (B < 1) return "batch must be >= 1";
+    if (p.num_legs < 1 || p.num_legs > DEKF_MAX_LEGS) return "num_legs out of range";
+    if (p.joints_per_leg < 1 || p.joints_per_leg > DEKF_MAX_JOINTS) return "joints_per_leg out of range";
+    if (p.leg_odom_type != 0 && p.leg_odom_type != 1) return "leg_odom_type must be 0 (foot velocity) or 1 (foot position)";
+    if (p.est_type != 0 && p.est_type != 1) return "est_type must be 0 (MHE) or 1 (KF)";
+    if (p.N < 2 || p.N > 128) return "N out of range [2,128]";
+    if (p.rate < 1 || p.ekf_rate < 1) return "rate must be positive";
+    if (p.ekf_history < 4) return "ekf_history must be >= 4";
+    if (p.polish != 0 && p.polish != 1) return "osqp.polish must be 0 or 1";
+    if (p.polish && !(p.delta > 0)) return "osqp.delta must be positive when osqp.polish is on";
+    // the polishing solve runs as an ADMM step with 1 / rho = delta on the equality rows, and rho lives in [RHO_MIN, RHO_MAX] * 1e3:
+    // outside this range the device would silently solve a differently regularised system than OSQP does
+    if (p.polish && !(p.delta >= 1e-9 && p.delta <= 1e3)) return "osqp.delta must lie in [1e-9, 1e3] when osqp.polish is on";
+    if (p.polish_refine_iter < 0 || p.polish_refine_iter > 100) return "polish_refine_iter out of range [0,100]";
+    if (p.arrival_cost_form != 0 && p.arrival_cost_form != 1) return "arrival_cost_form must be 0 (reference form) or 1 (information form)";
+    if (p.solve_pipeline != 0 && p.solve_pipeline != 1) return "solve_pipeline must be 0 (in order) or 1 (consecutive steps overlap)";
+    if (p.solve_workgroups_per_cu < 0 || p.solve_workgroups_per_cu > 8) return "solve_workgroups_per_cu out of range [0,8]";
+    if (const char* msg = check_noise(p)) return msg;
+    if (!(p.sigma > 0) || !(p.rho > 0) || !(p.alpha > 0 && p.alpha < 2)) return "rho/sigma/alpha out of range";
+    std::memset(&c, 0, sizeof(c));
+    c.B = B; c.L = p.num_legs; c.nj = p.joints_per_leg; c.N = p.N; c.nm = 3 * p.num_legs;
+    c.ft = p.leg_odom_type; c.ns = 9 + 3 * c.ft * c.L;
+    c.SV = 2 * c.ns + c.nm + 3; c.SC = c.nm + c.ns + 3;
+    // window records: N + 1 slots (the N of a window and the one the next step fills); one more when steps are pipelined, because
+    // the term construction of step T then runs while the solve of step T - 2 may still be reading its window (dekf_capi.hip)
+    c.ring = 4 * p.N + 1; c.wcap = p.N + 1 + ((p.solve_pipeline == 1 && p.est_type == 0) ? 1 : 0); c.rec = Rec::len(c.L, c.ft);
+    c.snap_len = c.ns * c.ns + c.ns + 4 * c.wcap;
+    c.est_type = p.est_type;
+    c.marg_info = p.leg_odom_type == 1 && p.arrival_cost_form == 1;
+    c.dt = 1.0 / (double)p.rate;
+    c.hdt2 = 0.5 * c.dt * c.dt;
+    c.gws_wt = 0;  // (dekf_create sets it once the placement of the factor is known)
+    c.inf_thr = OSQP_INFTY * MIN_SCALING;
     c.rho0 = p.rho; c.rho0c = p.rho < RHO_MIN ? RHO_MIN : (p.rho > RHO_MAX ? RHO_MAX : p.rho); c.sigma = p.sigma; c.alpha = p.alpha; c.eps_abs = p.abs_tol; c.eps_rel = p.rel_tol;
     c.max_iter = p.max_qp_iter; c.scaling = p.scaling_iters; c.check_termination = p.check_termination;
     c.adaptive_rho = p.adapt_rho; c.adaptive_rho_interval = p.adaptive_rho_interval;
@@ -116,12 +162,8 @@ inline const char* fill_cfg(const dekf_params& p, int B, DevCfg& c) {
     c.polish = p.polish; c.polish_refine_iter = p.polish_refine_iter; c.delta = p.delta;
     c.polish_accept_osqp = p.polish_accept_osqp != 0;
     c.ekf_dt = 1.0 / (double)p.ekf_rate;
-    for (int i = 0; i < 4; ++i) {
-        c.ekf_Cvo[i] = sq(p.ekf_vo_meas_std[i]);
-        c.ekf_P0[i] = sq(p.ekf_init_std[i]);
-        c.ekf_q0[i] = p.ekf_quaternion_init[i];
-    }
     c.ekf_hist = p.ekf_history;
+    fill_noise(p, c);
     return nullptr;
 }
 

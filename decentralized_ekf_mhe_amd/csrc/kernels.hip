@@ -11,6 +11,7 @@
 //   k_latch_vo        masked VO latch (robotSub::vo_callback for a batch)
 //   k_latch4          device-to-device sensor latch of one push (IMU or leg arrays) in one launch
 //   k_reset_instances, k_*_ep   restarting single instances of a direct handle (dekf_reset_instances, mhe_epoch_core.h)
+//   k_*_pp            the same with noise parameters per instance (dekf_set_instance_params, mhe_params_core.h)
 #include <hip/hip_runtime.h>
 
 #include "cfg.h"
@@ -20,6 +21,7 @@
 #include "mhe_assemble_core.h"
 #include "mhe_direct_core.h"
 #include "mhe_epoch_core.h"
+#include "mhe_params_core.h"
 #include "mhe_solve_core.h"
 
 using namespace dekf;
@@ -159,6 +161,25 @@ __global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_marginalize_early_ep
     extern __shared__ double lds[];
     marginalize_early_epoch(c, s, blockIdx.x, T, t0, lds);
 }
+
+// A direct handle with a parameter table (dekf_set_instance_params) launches these in place of the three above, from its first tick
+// on (every epoch 0 until an instance restarts): the same cores on every instance's own noise constants (mhe_params_core.h).
+// pe: the EKF table [PpEkf::len][B], a lane per instance; pc: the MHE table, a DevCfg per instance, whose address is uniform in the
+// workgroup: const __restrict__, so the cores read it through scalar loads as they read the kernel arguments.
+__global__ void __launch_bounds__(64) k_ekf_tick_pp(DevCfg c, DevState s, int count, const int* c0, const double* __restrict__ pe) {
+    int b = blockIdx.x * 64 + threadIdx.x;
+    if (b < c.B) ekf_tick_pp(c, s, b, count, c0, pe);
+}
+__global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_assemble_pp(DevState s, int T, int pushes, const int* t0,
+                                                                        const DevCfg* __restrict__ pc) {
+    extern __shared__ double lds[];
+    assemble_pp(pc, s, blockIdx.x, T, pushes, t0, lds);
+}
+__global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_marginalize_early_pp(DevState s, int T, const int* t0,
+                                                                                 const DevCfg* __restrict__ pc) {
+    extern __shared__ double lds[];
+    marginalize_early_pp(pc, s, blockIdx.x, T, t0, lds);
+}
 #endif  // DEKF_MISC_KERNELS
 
 // The solve kernels (solve_kernels.def).  One workgroup of DEKF_SOLVE_THREADS lanes (4 wavefronts, one per SIMD of the CU) per
@@ -221,6 +242,10 @@ __global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_marginalize_early_ep
 // dekf_reset_instances has restarted an instance: it takes the handle's step T in place of (kstart, K), reads its instance's epoch
 // t0[blockIdx.x] (one scalar load per workgroup) and calls the instantiation its sibling calls on the instance's local window, or
 // nothing at the instance's local step 0 (mhe_epoch_core.h).  The three siblings are the code they were.
+// And every epoch twin has its parameter twin NAME_pp, NAME_smooth_pp, NAME_smooth_cross_pp, which a handle with a parameter table
+// launches (dekf_set_instance_params): the epoch twin on its instance's DevCfg of the table (pc[blockIdx.x], scalar loads from a
+// workgroup-uniform address) in place of the handle's in the kernel arguments (mhe_params_core.h).  Of the noise constants the direct
+// solve reads Q_bias_dt2 alone; the rest is in the window records the assemble step wrote.
 #define DEKF_DIRECT_EPOCH_TWINS_(NAME, L, FT)                                                                                 \
     __global__ void __launch_bounds__(64) NAME##_ep(DevCfg c, DevState s, int T, double* cov, const int* t0) {               \
         extern __shared__ double lds[];                                                                                      \
@@ -237,6 +262,29 @@ __global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_marginalize_early_ep
                                                                  DirectCross cross, const int* t0) {                         \
         extern __shared__ double lds[];                                                                                      \
         int kstart, K;                                                                                                       \
+        if (direct_window_epoch(c, T, t0[blockIdx.x], kstart, K))                                                            \
+            direct_solve_t<L, FT, true, true>(c, s, blockIdx.x, kstart, K, lds, cov, win, cross);                             \
+    }                                                                                                                        \
+    __global__ void __launch_bounds__(64) NAME##_pp(DevState s, int T, double* cov, const int* t0,                           \
+                                                    const DevCfg* __restrict__ pc) {                                         \
+        extern __shared__ double lds[];                                                                                      \
+        int kstart, K;                                                                                                       \
+        const DevCfg& c = pc[blockIdx.x];                                                                                    \
+        if (direct_window_epoch(c, T, t0[blockIdx.x], kstart, K)) direct_solve_t<L, FT>(c, s, blockIdx.x, kstart, K, lds, cov); \
+    }                                                                                                                        \
+    __global__ void __launch_bounds__(64) NAME##_smooth_pp(DevState s, int T, double* cov, DirectWindow win, const int* t0, \
+                                                           const DevCfg* __restrict__ pc) {                                  \
+        extern __shared__ double lds[];                                                                                      \
+        int kstart, K;                                                                                                       \
+        const DevCfg& c = pc[blockIdx.x];                                                                                    \
+        if (direct_window_epoch(c, T, t0[blockIdx.x], kstart, K))                                                            \
+            direct_solve_t<L, FT, true>(c, s, blockIdx.x, kstart, K, lds, cov, win);                                          \
+    }                                                                                                                        \
+    __global__ void __launch_bounds__(64) NAME##_smooth_cross_pp(DevState s, int T, double* cov, DirectWindow win,            \
+                                                                 DirectCross cross, const int* t0, const DevCfg* __restrict__ pc) { \
+        extern __shared__ double lds[];                                                                                      \
+        int kstart, K;                                                                                                       \
+        const DevCfg& c = pc[blockIdx.x];                                                                                    \
         if (direct_window_epoch(c, T, t0[blockIdx.x], kstart, K))                                                            \
             direct_solve_t<L, FT, true, true>(c, s, blockIdx.x, kstart, K, lds, cov, win, cross);                             \
     }
@@ -264,7 +312,10 @@ __global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_marginalize_early_ep
     __global__ void NAME##_smooth_cross(DevCfg, DevState, int, int, double*, DirectWindow, DirectCross) {} \
     __global__ void NAME##_ep(DevCfg, DevState, int, double*, const int*) {} \
     __global__ void NAME##_smooth_ep(DevCfg, DevState, int, double*, DirectWindow, const int*) {} \
-    __global__ void NAME##_smooth_cross_ep(DevCfg, DevState, int, double*, DirectWindow, DirectCross, const int*) {}
+    __global__ void NAME##_smooth_cross_ep(DevCfg, DevState, int, double*, DirectWindow, DirectCross, const int*) {} \
+    __global__ void NAME##_pp(DevState, int, double*, const int*, const DevCfg*) {} \
+    __global__ void NAME##_smooth_pp(DevState, int, double*, DirectWindow, const int*, const DevCfg*) {} \
+    __global__ void NAME##_smooth_cross_pp(DevState, int, double*, DirectWindow, DirectCross, const int*, const DevCfg*) {}
 #endif
 #include "direct_kernels.def"
 
@@ -333,6 +384,23 @@ __global__ void k_reset_instances(DevCfg c, DevState s, const int* mask, double*
 __global__ void k_fold_epochs(int* c0, int B, int count_old, int count_new, int H) {
     int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < B) c0[b] = fold_epoch(c0[b], count_old, count_new, H);
+}
+
+// dekf_reset_instances and dekf_reset of a handle with a parameter table: every instance's own initial EKF state (mhe_params_core.h);
+// and dekf_set_instance_params itself, for the instances of its mask (all of them at local tick 0 or -1)
+__global__ void k_reset_instances_pp(DevCfg c, DevState s, const int* mask, double* cov, int* t0, int* c0, int next_T, int ekf_count,
+                                     const double* __restrict__ pe) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= c.B || !mask[b]) return;
+    reset_instance_pp(c, s, b, cov, t0, c0, next_T, ekf_count, pe);
+}
+__global__ void k_reset_state_pp(DevCfg c, DevState s, const double* __restrict__ pe) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < c.B) reset_state_pp(c, s, b, pe);  // (a direct handle has no warm store)
+}
+__global__ void k_ekf_init_pp(DevCfg c, DevState s, const int* mask, const double* __restrict__ pe) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < c.B && mask[b]) ekf_init_pp(c, s, b, pe);
 }
 
 __global__ void k_reset_state(DevCfg c, DevState s) {

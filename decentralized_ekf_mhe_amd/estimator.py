@@ -170,6 +170,25 @@ class BatchedEstimator:
         capi.check(self.lib.dekf_get_instance_ticks(self.h, C.c_void_p(t.ctypes.data), capi.DEKF_HOST))
         return t
 
+    def set_instance_params(self, sets, set_of):
+        """noise parameters per instance of a direct handle (dekf_set_instance_params): sets, a sequence of DekfParams that differ from
+        the handle's in noise fields only; set_of, B ints: instance b takes sets[set_of[b]], -1 leaves it as it is.  Before the first
+        tick (or right after reset()) for any instance, later only for instances that reset_instances has just restarted.
+        sets=None (or empty) with set_of=None drops the table"""
+        if not sets and set_of is None:
+            capi.check(self.lib.dekf_set_instance_params(self.h, None, 0, None))
+            return
+        arr = (DekfParams * len(sets))(*[s.copy() for s in sets])
+        so = np.ascontiguousarray(set_of, np.int32)
+        assert so.shape == (self.batch,), so.shape
+        capi.check(self.lib.dekf_set_instance_params(self.h, C.cast(arr, C.c_void_p), len(sets), C.c_void_p(so.ctypes.data)))
+
+    def instance_params(self, b):
+        """the handle's parameters with instance b's noise fields (dekf_get_instance_params)"""
+        out = DekfParams()
+        capi.check(self.lib.dekf_get_instance_params(self.h, int(b), C.byref(out)))
+        return out
+
     def sync(self):
         capi.check(self.lib.dekf_sync(self.h))
 

@@ -367,9 +367,48 @@ dekf_status dekf_get_window_cross(dekf_handle h, int* steps, double* cov_lag1, d
  * restarted one, T - T0 after a restart before step T0 (-1 between the restart and dekf_update(h, T0)); K_b = min(ticks[b] + 1, N)
  * once ticks[b] >= 1.  Any initialised handle; DEKF_ERR_ORDER before dekf_initialize, DEKF_ERR_INVALID for a null handle or pointer.
  * Not part of this interface: ADMM handles (their launch takes one window length for the batch), KF and pipelined handles, instances
- * that are switched off, parameters per instance. */
+ * that are switched off.  (Parameters per instance: dekf_set_instance_params below.) */
 dekf_status dekf_reset_instances(dekf_handle h, const int* mask, dekf_mem where);
 dekf_status dekf_get_instance_ticks(dekf_handle h, int* ticks, dekf_mem where);
+
+/* ---- noise parameters per instance (direct handles): every robot of a handle its own noise ------------------------------
+ * Two more additive symbols: DEKF_ABI_VERSION and dekf_params are unchanged, and a caller that never calls them launches exactly the
+ * kernels of before and gets the same bits.  A handle estimates thousands of robots with one dekf_params; with a parameter table
+ * every instance has its own NOISE FIELDS (noise tuning: B candidate sets on one log in one launch per tick; a vectorised simulator
+ * that draws new sensor-noise levels for a restarted environment; a mixed fleet):
+ *     p_init_std v_init_std foot_init_std accel_bias_init_std p_process_std accel_input_std gyro_input_std accel_bias_std
+ *     joint_position_std joint_velocity_std foot_slide_std foot_swing_std vo_p_std
+ *     ekf_init_std ekf_process_std ekf_gravity_meas_std ekf_vo_meas_std ekf_quaternion_init
+ * dekf_set_instance_params(h, sets, nsets, set_of): sets[nsets] and set_of[B] are host pointers; set_of[b] in 0 .. nsets - 1 gives
+ * instance b the noise fields of that set, set_of[b] = -1 leaves instance b as it is (on the handle's own parameters if it never took
+ * a set).  nsets = 0 with both pointers NULL drops the table: every instance is on the handle's parameters again and the handle
+ * launches its former kernels (before the first tick or right after dekf_reset only, else DEKF_ERR_ORDER).
+ *  - Every other field of every set must equal the handle's own parameters: structure, rates, N, the osqp.* block,
+ *    contact_effort_threshold, p_ib, quaternion_ib, the form switches and launch tuning; else DEKF_ERR_INVALID: a difference is
+ *    refused, never ignored.  The positivity that dekf_create asks of the foot stds (leg_odom_type 1) is asked of every set.
+ *  - Where: direct handles only.  DEKF_ERR_INVALID for ADMM and KF handles, for solve_pipeline = 1, a null handle, an index outside
+ *    -1 .. nsets - 1, nsets < 0, and for pointers that do not go with nsets.  dekf_set_solver(h, DEKF_SOLVER_ADMM) on a handle that
+ *    has a table is DEKF_ERR_INVALID: drop the table first.
+ *  - When: before the first dekf_ekf_step (since dekf_create or dekf_reset): any instance.  On a running handle only instances whose
+ *    local tick (dekf_get_instance_ticks) is -1, i.e. restarted by dekf_reset_instances, before the next dekf_ekf_step.  Any other
+ *    instance with set_of[b] >= 0 makes the whole call DEKF_ERR_ORDER and nothing is applied: an instance never changes parameters in
+ *    mid-life.
+ *  - The call rewrites the EKF state of the instances it names to their set's initial quaternion and covariance, and returns when
+ *    the table is on the device.
+ *  - The table survives dekf_reset, as the other settings do, and dekf_reset_instances: a restarted instance keeps its set until
+ *    told otherwise, and both calls write every instance's own initial EKF state.
+ *  - From its first tick on every output of instance b (dekf_get, dekf_get_ekf_cov, dekf_get_mhe_cov, dekf_get_solver_info,
+ *    dekf_get_window, dekf_get_window_cross) is bit-identical to instance b of a handle created with sets[set_of[b]] (same batch, same
+ *    samples); after a restart, to a fresh handle with that set fed the samples from the restart on.  The derived constants are
+ *    computed on the host by the expressions dekf_create uses.
+ *  - A handle with a table launches the parameter twins of the epoch kernels from its first tick on: dekf_solve_kernel_name names
+ *    k_mhe_solve_direct_*_pp, *_smooth_pp or *_smooth_cross_pp.
+ * dekf_get_instance_params(h, b, out): the handle's parameters with instance b's noise fields; on any handle (without a table: the
+ * handle's own parameters).  DEKF_ERR_INVALID for b outside 0 .. B - 1 or a null pointer.
+ * Not part of this interface: ADMM, KF and pipelined handles; structure, rates, horizon, solver settings, contact_effort_threshold
+ * or the IMU-to-body transform per instance; instances that are switched off. */
+dekf_status dekf_set_instance_params(dekf_handle h, const dekf_params* sets, int nsets, const int* set_of);
+dekf_status dekf_get_instance_params(dekf_handle h, int b, dekf_params* out);
 
 /* status[B] values written by dekf_update */
 #define DEKF_SOLVE_NONE 0       /* no solve yet (T = 0) */

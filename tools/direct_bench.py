@@ -18,7 +18,11 @@ alternate inside one process, so that a drift of the machine does not land on on
 --epoch measures what dekf_reset_instances costs the instances it does not restart: per mode ONE handle runs the unchanged direct
 kernel (`before`), then restarts instance 0, lets its window refill and runs the epoch twins (`after`); dekf_reset brings the handle
 back, and the two alternate --repeat times in one process.  One JSON line per shape (--out: profiles/r11_epoch_bench.jsonl).
-    python tools/direct_bench.py go1 --epoch --modes direct,direct_smooth,direct_cross --steps 80 --repeat 3"""
+    python tools/direct_bench.py go1 --epoch --modes direct,direct_smooth,direct_cross --steps 80 --repeat 3
+--instance-params measures what a parameter table (dekf_set_instance_params) costs: per mode ONE handle runs the unchanged direct
+kernels (`before`: no table), then, after dekf_reset, the _pp twins with B distinct sets (`after`), and the two alternate --repeat
+times in one process.  One JSON line per shape (--out: profiles/r12_instance_params_bench.jsonl).
+    python tools/direct_bench.py go1 --instance-params --modes direct,direct_smooth,direct_cross --repeat 3"""
 import argparse
 import json
 import os
@@ -144,6 +148,54 @@ def epoch_runs(p, B, sd, steps, mode, repeat):
             "steps_per_s_after_over_before": a["steps_per_s"] / b["steps_per_s"]}
 
 
+def distinct_sets(p, B):
+    """B parameter sets, no two alike: every std of the noise fields scaled by a factor of its own in [0.8, 1.25]"""
+    fields = ("p_init_std", "v_init_std", "foot_init_std", "accel_bias_init_std", "p_process_std", "accel_input_std", "gyro_input_std",
+              "accel_bias_std", "joint_position_std", "joint_velocity_std", "foot_slide_std", "foot_swing_std", "vo_p_std", "ekf_init_std",
+              "ekf_process_std", "ekf_gravity_meas_std", "ekf_vo_meas_std")
+    sets = []
+    for b in range(B):
+        q = p.copy()
+        for i, f in enumerate(fields):
+            a = getattr(q, f)
+            for j in range(len(a)):
+                a[j] = a[j] * (0.8 + 0.45 * ((b * 7 + i * 3 + j) % B) / B)
+        sets.append(q)
+    return sets
+
+
+def instance_params_runs(p, B, sd, steps, mode, repeat):
+    """without / with a parameter table of B distinct sets on one handle, `repeat` times in turn (dekf_reset in between)"""
+    import numpy as np
+    W = max(p.N + 10, 64)
+    est = BatchedEstimator(p, B, **MODES[mode])
+    sets, set_of = distinct_sets(p, B), np.arange(B, dtype=np.int32)
+    before, after = [], []
+    for _ in range(repeat):
+        for runs, table in ((before, False), (after, True)):
+            est.reset()
+            est.set_instance_params(sets if table else None, set_of if table else None)
+            for k in range(W):
+                est.push_stream_step(sd, k)
+                est.step(k)
+            runs.append(timed(est, sd, W, steps, B))
+            assert runs[-1]["kernel"].endswith("_pp") == table
+            assert float((est.get()["status"] == 1).mean()) == 1.0
+    est.close()
+
+    def best(runs):
+        out = dict(max(runs, key=lambda r: r["steps_per_s"]))
+        for c in ("solve", "assemble", "ekf"):
+            out[f"{c}_ms"] = min(r[f"{c}_ms"] for r in runs)
+        out["all_steps_per_s"] = [r["steps_per_s"] for r in runs]
+        out["all_solve_ms"] = [r["solve_ms"] for r in runs]
+        return out
+    b, a = best(before), best(after)
+    return {"before": b, "after": a, "solve_ms_after_over_before": a["solve_ms"] / b["solve_ms"],
+            "assemble_ms_after_over_before": a["assemble_ms"] / b["assemble_ms"], "ekf_ms_after_over_before": a["ekf_ms"] / b["ekf_ms"],
+            "steps_per_s_after_over_before": a["steps_per_s"] / b["steps_per_s"]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("shapes", nargs="*", default=list(SHAPES))
@@ -152,8 +204,11 @@ def main():
     ap.add_argument("--repeat", type=int, default=1)
     ap.add_argument("--out", default=None)
     ap.add_argument("--epoch", action="store_true", help="the same handle before and after a first dekf_reset_instances")
+    ap.add_argument("--instance-params", action="store_true", help="the same handle without and with a table of B distinct parameter sets")
     a = ap.parse_args()
     modes = a.modes.split(",")
+    if a.out is None and a.instance_params:
+        a.out = os.path.join(ROOT, "profiles", "r12_instance_params_bench.jsonl")
     if a.out is None and a.epoch:
         a.out = os.path.join(ROOT, "profiles", "r11_epoch_bench.jsonl")
     if a.out is None:
@@ -165,6 +220,16 @@ def main():
         p.ekf_rate = p.rate
         for k, v in kw.items():
             setattr(p, k, v)
+        if a.instance_params:
+            sd = streams_to_device(make_streams(p, B, max(p.N + 10, 64) + 2 * a.steps))
+            line = {"shape": name, "batch": B, "N": int(p.N), "steps": a.steps, "repeat": a.repeat, "instance_params": True}
+            line.update({mode: instance_params_runs(p, B, sd, a.steps, mode, a.repeat) for mode in modes})
+            print(json.dumps(line), flush=True)
+            with open(a.out, "a") as f:
+                f.write(json.dumps(line) + "\n")
+            del sd
+            torch.cuda.empty_cache()
+            continue
         if a.epoch:
             sd = streams_to_device(make_streams(p, B, epoch_ticks(p, a.steps)[2]))
             line = {"shape": name, "batch": B, "N": int(p.N), "steps": a.steps, "repeat": a.repeat, "epoch": True}
