@@ -116,22 +116,22 @@ struct dekf_handle_s {
     DirectCross cross_st;
     // dekf_reset_instances: the epochs of a direct handle (mhe_epoch_core.h).  ep_t0 | ep_c0: [B] ints each on the device, the handle's
     // step and EKF tick count at every instance's last restart (0: never), allocated by the first call with a non-zero mask; t0_host:
-    // the host's copy of ep_t0 (dekf_get_instance_ticks, the window getters' steps), min_t0 its smallest entry.  epochs: a non-zero
-    // mask has been applied since dekf_create / dekf_reset — the handle launches the *_ep kernels, which take the two arrays
+    // the host's copy of ep_t0 (dekf_get_instance_ticks, the window getters' steps), min_t0 its smallest entry; c0_host: the host's copy
+    // of ep_c0 (dekf_set_instance_params: an instance whose c0 is the handle's count has not ticked since its restart), folded with
+    // ep_c0.  epochs: a non-zero mask has been applied since dekf_create / dekf_reset — the handle launches the *_ep kernels, which
+    // take the two arrays
     int *ep_t0 = nullptr, *ep_c0 = nullptr;
-    std::vector<int> t0_host;
+    std::vector<int> t0_host, c0_host;
     int min_t0 = 0;
     bool epochs = false;
     // dekf_set_instance_params: the noise constants of every instance of a direct handle (mhe_params_core.h).  pp_mhe [B] DevCfg
     // and pp_ekf [PpEkf::len][B] on the device, allocated by the first call that sets a table; inst_prm: the handle's parameters with
     // every instance's noise fields (dekf_get_instance_params).  pp: the handle has a table: it launches the *_pp kernels, which are
-    // the epoch kernels with the table as one more argument, so the epoch arrays exist (all 0 unless `epochs`).  ekf_ticked: a
-    // dekf_ekf_step since the last dekf_update / dekf_initialize / dekf_reset: the instances at local tick -1 are no longer at EKF tick 0
+    // the epoch kernels with the table as one more argument, so the epoch arrays exist (all 0 unless `epochs`)
     DevCfg* pp_mhe = nullptr;
     double* pp_ekf = nullptr;
     std::vector<dekf_params> inst_prm;
     bool pp = false;
-    bool ekf_ticked = false;
     size_t lds_solve = 0, lds_asm = 0, lds_kf = 0;
     int ekf_count = 0, pushes = 0, next_T = 0;
     bool initialized = false;
@@ -450,6 +450,7 @@ dekf_status ensure_epochs(dekf_handle h) {
     h->ep_t0 = e;
     h->ep_c0 = e + B;
     h->t0_host.assign(B, 0);
+    h->c0_host.assign(B, 0);
     h->min_t0 = 0;
     return DEKF_OK;
 }
@@ -787,12 +788,12 @@ dekf_status dekf_reset(dekf_handle h) {
     }
     h->last_par = h->ekf_count = h->pushes = h->next_T = 0;
     h->initialized = false;
-    h->ekf_ticked = false;
     h->mhe_cov_valid = false;  // (the solver, smoother and cross settings survive)
     h->win_steps = 0;
     if (h->ep_t0) {  // every epoch: the handle launches the kernels of a handle that never restarted an instance again
         HIPCHK(hipMemsetAsync(h->ep_t0, 0, 2 * (size_t)h->c.B * sizeof(int), h->stream));
         h->t0_host.assign((size_t)h->c.B, 0);
+        h->c0_host.assign((size_t)h->c.B, 0);
         h->min_t0 = 0;
         h->epochs = false;
     }
@@ -836,7 +837,7 @@ dekf_status dekf_reset_instances(dekf_handle h, const int* mask, dekf_mem where)
     if (where == DEKF_HOST) HIPCHK(hipStreamSynchronize(h->stream));  // (m, a local, is the source of the copy)
     h->min_t0 = h->next_T;
     for (size_t b = 0; b < B; ++b) {
-        if (m[b]) h->t0_host[b] = h->next_T;
+        if (m[b]) { h->t0_host[b] = h->next_T; h->c0_host[b] = h->ekf_count; }
         if (h->t0_host[b] < h->min_t0) h->min_t0 = h->t0_host[b];
     }
     h->epochs = true;
@@ -896,8 +897,9 @@ dekf_status dekf_set_instance_params(dekf_handle h, const dekf_params* sets, int
     if (!fresh)
         for (size_t b = 0; b < B; ++b) {
             if (set_of[b] < 0) continue;
-            // only an instance that dekf_reset_instances has restarted and that has seen neither an update nor an EKF tick since
-            const bool restarted = h->initialized && h->epochs && T - h->t0_host[b] == -1 && !h->ekf_ticked;
+            // only an instance that dekf_reset_instances has restarted and that has seen neither an update nor an EKF tick since:
+            // its own local step is -1 and its own local EKF count 0, whatever the handle ticked before the restart
+            const bool restarted = h->initialized && h->epochs && T - h->t0_host[b] == -1 && h->ekf_count == h->c0_host[b];
             if (!restarted)
                 return fail(DEKF_ERR_ORDER, "dekf_set_instance_params: an instance takes a set before its first tick only (before the first "
                                             "dekf_ekf_step, right after dekf_reset, or right after dekf_reset_instances restarted it)");
@@ -1033,7 +1035,6 @@ dekf_status dekf_ekf_step(dekf_handle h) {
     }
     HIPCHK(hipGetLastError());
     h->ekf_count++;
-    h->ekf_ticked = true;
     // the kernel uses the count only modulo the ring depth and to know whether the ring is full: folded long before
     // the int overflows (a 500 Hz node reaches 2^31 ticks after 49 days)
     if (h->ekf_count >= (1 << 30)) {
@@ -1043,6 +1044,7 @@ dekf_status dekf_ekf_step(dekf_handle h) {
         if (h->epochs) {
             k_fold_epochs<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->ep_c0, h->c.B, h->ekf_count, folded, h->c.ekf_hist);
             HIPCHK(hipGetLastError());
+            for (int& c0 : h->c0_host) c0 = fold_epoch(c0, h->ekf_count, folded, h->c.ekf_hist);  // (the host's copy moves alike)
         }
         h->ekf_count = folded;
     }
@@ -1064,7 +1066,6 @@ dekf_status dekf_initialize(dekf_handle h) {
     HIPCHK(hipGetLastError());
     h->last_par = 0;
     h->initialized = true;
-    h->ekf_ticked = false;
     h->next_T = 1;
     return DEKF_OK;
 }
@@ -1086,7 +1087,6 @@ dekf_status dekf_update(dekf_handle h, int T) {
     HIPCHK(hipGetLastError());
     h->pushes++;
     h->next_T++;
-    h->ekf_ticked = false;
     return DEKF_OK;
 }
 

@@ -344,18 +344,23 @@ dekf_status dekf_get_window_cross(dekf_handle h, int* steps, double* cov_lag1, d
  * vectorised simulator) while every other instance keeps its window, its arrival cost and every bit of every output.
  * dekf_reset_instances(h, mask, where): mask[B], 1 restarts the instance, 0 leaves it alone; a host or a device pointer (a device mask
  * is copied to the host and waited for: the call checks it).
- *  - When: on an initialised direct handle between dekf_update(h, T0 - 1) and the pushes of step T0, i.e. before that step's
- *    dekf_ekf_step.  DEKF_ERR_ORDER before dekf_initialize.  DEKF_ERR_INVALID for a null handle or mask, for a handle that is not a
+ *  - When: on an initialised direct handle anywhere between dekf_update(h, T0 - 1) and dekf_update(h, T0).  On a lock-step handle
+ *    (one dekf_ekf_step per update) that is before the pushes and the dekf_ekf_step of step T0.  On a two-rate handle (ekf_rate above
+ *    rate: several dekf_ekf_step between two updates) the call may come before, between or behind the EKF ticks of that gap: the
+ *    ticks before the call belong to the instance's earlier life, the ticks behind it to the new one.  IMU and leg samples are pushed
+ *    at least once between the call and dekf_update(h, T0), as before any dekf_initialize.  DEKF_ERR_ORDER before dekf_initialize.  DEKF_ERR_INVALID for a null handle or mask, for a handle that is not a
  *    direct handle (ADMM, KF) or has solve_pipeline = 1, and for a mask entry other than 0 or 1.  The handle's stream waits for what
  *    dekf_reset waits for (solves in flight, the arrival cost computed ahead, readers of v_b) before the instances are cleared.
  *  - A restarted instance is as after dekf_reset: EKF state and covariance at their initial values, VO latches, way points and the
  *    p_vo accumulator cleared, x_mhe and v_b 0, status DEKF_SOLVE_NONE, solver info 0; its block of dekf_get_mhe_cov is NaN until its
  *    first solve.  A sample latched before the call is dropped for it; the samples pushed after the call are its first.
- *  - Its next dekf_ekf_step is its EKF tick 0; dekf_update(h, T0) is its dekf_initialize (first sample, prior as arrival cost, no
+ *  - Its next dekf_ekf_step is its EKF tick 0, however many ticks the handle has run (since its last update too); dekf_update(h, T0)
+ *    is its dekf_initialize (first sample, prior as arrival cost, no
  *    solve) and dekf_update(h, T0 + j) its update(j), with a window of K_b = min(j + 1, N) steps.
  *  - From step T0 on every output of the instance (dekf_get, dekf_get_ekf_cov, dekf_get_mhe_cov, dekf_get_solver_info and the first K_b
  *    entries of dekf_get_window and dekf_get_window_cross) is bit-identical to the same instance of a fresh handle that is fed the same
- *    samples from step T0 on.  The instances outside the mask keep every bit of every output at every later step.
+ *    samples and runs the same calls FROM THE CALL on: its first dekf_ekf_step is the first one behind the call, its
+ *    dekf_initialize stands where dekf_update(h, T0) does.  The instances outside the mask keep every bit of every output at every later step.
  *  - An all-zero mask changes nothing.  An instance may be restarted again at any later step, inside its own window fill too.
  *  - *steps of dekf_get_window and dekf_get_window_cross becomes the largest K_b of the batch; entries k >= K_b of instance b (k >= K_b - 1
  *    of cov_lag1) are not specified.  The two getters return DEKF_ERR_ORDER while no instance has solved since its restart.
@@ -390,8 +395,10 @@ dekf_status dekf_get_instance_ticks(dekf_handle h, int* ticks, dekf_mem where);
  *    -1 .. nsets - 1, nsets < 0, and for pointers that do not go with nsets.  dekf_set_solver(h, DEKF_SOLVER_ADMM) on a handle that
  *    has a table is DEKF_ERR_INVALID: drop the table first.
  *  - When: before the first dekf_ekf_step (since dekf_create or dekf_reset): any instance.  On a running handle only instances whose
- *    local tick (dekf_get_instance_ticks) is -1, i.e. restarted by dekf_reset_instances, before the next dekf_ekf_step.  Any other
- *    instance with set_of[b] >= 0 makes the whole call DEKF_ERR_ORDER and nothing is applied: an instance never changes parameters in
+ *    local tick (dekf_get_instance_ticks) is -1 and that have not ticked since, i.e. restarted by dekf_reset_instances and before
+ *    the next dekf_ekf_step behind THAT restart.  The rule is per instance: EKF ticks of the handle before the restart (a two-rate
+ *    handle runs several between two updates) do not count, and of two instances restarted in one gap with a tick between them
+ *    only the later one still takes a set.  Any other instance with set_of[b] >= 0 makes the whole call DEKF_ERR_ORDER and nothing is applied: an instance never changes parameters in
  *    mid-life.
  *  - The call rewrites the EKF state of the instances it names to their set's initial quaternion and covariance, and returns when
  *    the table is on the device.

@@ -135,39 +135,45 @@ def cross_errors(l1, zn, Cf):
 
 
 # ------------------------------------------------------------------ the oracle reference
-def kkt_reference(p, s, b, ticks, arrival=None, solve=True, invert=True):
-    """Instance b through the oracle's pipe; at every tick in `ticks` yields (tick, x, Ki, xo, VO equality rows): x the exact optimum
-    of the oracle's window QP (kkt_exact; None without `solve`), Ki the inverse of its KKT matrix, equilibrated as kkt_exact does (its
-    (1, 1) block is the covariance of the window's variables; None without `invert`), xo the offsets of the K window states in both,
-    oldest first, and how many of the window's VO rows are equalities.
-    arrival: {tick: (M_p, n_p)} put in place of the oracle's arrival cost on the first block (1/2 x'M_p x + n_p'x)"""
+def kkt_of_qp(p, qp, k, arrival=None, solve=True, invert=True):
+    """(x, Ki, xo, VO equality rows) of the window QP `qp` (Est.qp()) of an estimator at its step k >= 1: x the exact optimum
+    (kkt_exact; None without `solve`), Ki the inverse of the KKT matrix, equilibrated as kkt_exact does (its (1, 1) block is the
+    covariance of the window's variables; None without `invert`), xo the offsets of the K window states in both, oldest first
+    (SURVEY.md Appendix A), and how many of the window's VO rows are equalities.
+    arrival: (M_p, n_p) put in place of the oracle's arrival cost on the first block (1/2 x'M_p x + n_p'x)"""
     ns, nm = p.dim_state, 3 * p.num_legs
     sv = 2 * ns + nm + 3
+    H, g, A, l, u = qp
+    if arrival is not None:
+        H, g = H.copy(), g.copy()
+        H[:ns, :ns], g[:ns] = arrival
+    n = H.shape[0]
+    K = (n - ns - nm) // sv + 1
+    assert K == min(k + 1, p.N) and (ns + nm) + (K - 1) * sv == n
+    xo = [0 if j == 0 else (ns + nm) + (j - 1) * sv + ns + 3 for j in range(K)]
+    assert xo[K - 1] == n - ns - nm
+    x = RN.kkt_exact(H, g, A, l, u)[0] if solve else None
+    Ki = None
+    if invert:
+        eq = (u - l) < 1e-9
+        Ae = A[eq]
+        KK = np.zeros((n + Ae.shape[0],) * 2)
+        KK[:n, :n], KK[:n, n:], KK[n:, :n] = H, Ae.T, Ae
+        d = 1.0 / np.sqrt(np.maximum(np.abs(KK).max(axis=1), 1e-300))
+        Ki = np.linalg.inv(KK * d[:, None] * d[None, :]) * d[:, None] * d[None, :]
+    return x, Ki, xo, vo_equalities(p, A, l)
+
+
+def kkt_reference(p, s, b, ticks, arrival=None, solve=True, invert=True):
+    """Instance b through the oracle's pipe; at every tick in `ticks` yields (tick, x, Ki, xo, VO equality rows): kkt_of_qp of the
+    oracle's window QP at that tick.  arrival: {tick: (M_p, n_p)} put in place of the oracle's arrival cost"""
     pipe = O.Pipe(p)
     for k in range(max(ticks) + 1):
         pipe.feed(s, k, b)
         pipe.step(k)
         if k not in ticks:
             continue
-        H, g, A, l, u = pipe.est.qp()
-        if arrival is not None:
-            H, g = H.copy(), g.copy()
-            H[:ns, :ns], g[:ns] = arrival[k]
-        n = H.shape[0]
-        K = (n - ns - nm) // sv + 1
-        assert K == min(k + 1, p.N) and (ns + nm) + (K - 1) * sv == n
-        xo = [0 if j == 0 else (ns + nm) + (j - 1) * sv + ns + 3 for j in range(K)]
-        assert xo[K - 1] == n - ns - nm
-        x = RN.kkt_exact(H, g, A, l, u)[0] if solve else None
-        Ki = None
-        if invert:
-            eq = (u - l) < 1e-9
-            Ae = A[eq]
-            KK = np.zeros((n + Ae.shape[0],) * 2)
-            KK[:n, :n], KK[:n, n:], KK[n:, :n] = H, Ae.T, Ae
-            d = 1.0 / np.sqrt(np.maximum(np.abs(KK).max(axis=1), 1e-300))
-            Ki = np.linalg.inv(KK * d[:, None] * d[None, :]) * d[:, None] * d[None, :]
-        yield k, x, Ki, xo, vo_equalities(p, A, l)
+        yield (k,) + kkt_of_qp(p, pipe.est.qp(), k, None if arrival is None else arrival[k], solve, invert)
 
 
 def exact_reference(p, s, b, ticks, cov=True, arrival=None):
@@ -396,8 +402,15 @@ class DirectSim(HL.HostSim):
         self.win = {}
         self.K = 0
 
-    def step(self, T):
+    def ekf_step(self):
         self.L.hs_ekf_step(self.h)
+
+    def step(self, T):
+        self.ekf_step()
+        self.update(T)
+
+    def update(self, T):
+        """the MHE timer's event alone: hs_initialize at T = 0, else the variant's update"""
         if T == 0:
             self.L.hs_initialize(self.h)
             return

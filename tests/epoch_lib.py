@@ -91,6 +91,7 @@ def epoch_hostsim():
         L.hs_reset_instances.argtypes = [vp, vp, ip, dp]
         L.hs_ekf_step_epoch.argtypes = [vp, vp]
         L.hs_instance_ticks.argtypes = [vp, C.c_int, ip]
+        L.hs_epochs_copy.argtypes = [vp, ip, ip]
         L.hs_update_direct_epoch.argtypes = [vp, vp, C.c_int, dp]
         L.hs_update_direct_smooth_epoch.argtypes = [vp, vp, C.c_int, dp, dp, dp]
         L.hs_update_direct_cross_epoch.argtypes = [vp, vp, C.c_int, dp, dp, dp, dp, dp]
@@ -131,9 +132,22 @@ class EpochSim(HL.HostSim):
         self.L.hs_instance_ticks(self.e, T, HL._p(t))
         return t
 
-    def step(self, T):
-        ns, N, B = self.p.dim_state, self.p.N, self.B
+    def epochs(self):
+        """(t0, c0): the handle's step and its EKF tick count at every instance's last restart"""
+        t0, c0 = np.zeros(self.B, np.int32), np.zeros(self.B, np.int32)
+        self.L.hs_epochs_copy(self.e, HL._p(t0), HL._p(c0))
+        return t0, c0
+
+    def ekf_step(self):
         self.L.hs_ekf_step_epoch(self.h, self.e)
+
+    def step(self, T):
+        self.ekf_step()
+        self.update(T)
+
+    def update(self, T):
+        """the MHE timer's event alone (T = 0: every instance takes the initialise path)"""
+        ns, N, B = self.p.dim_state, self.p.N, self.B
         if self.variant == "plain":
             self.L.hs_update_direct_epoch(self.h, self.e, T, HL._p(self.cov))
             return

@@ -68,6 +68,11 @@ void hs_instance_ticks(void* ev, int T, int* ticks) {
     Epochs* ep = (Epochs*)ev;
     for (size_t b = 0; b < ep->t0.size(); ++b) ticks[b] = T - ep->t0[b];
 }
+// the two epoch arrays as they stand ([B] each)
+void hs_epochs_copy(void* ev, int* t0, int* c0) {
+    Epochs* ep = (Epochs*)ev;
+    for (size_t b = 0; b < ep->t0.size(); ++b) { t0[b] = ep->t0[b]; c0[b] = ep->c0[b]; }
+}
 // hs_update_direct* (direct_hostsim.cpp) with epochs
 void hs_update_direct_epoch(void* hv, void* ev, int T, double* cov) { update_direct_epoch<false, false>((Sim*)hv, (Epochs*)ev, T, cov); }
 void hs_update_direct_smooth_epoch(void* hv, void* ev, int T, double* cov, double* x_win, double* cov_win) {

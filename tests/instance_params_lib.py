@@ -91,6 +91,7 @@ def params_hostsim():
         L.hs_epochs_create.argtypes = [C.c_int]
         L.hs_epochs_destroy.argtypes = [vp]
         L.hs_instance_ticks.argtypes = [vp, C.c_int, ip]
+        L.hs_epochs_copy.argtypes = [vp, ip, ip]
         L.hs_tables_create.restype = vp
         L.hs_tables_create.argtypes = [vp]
         L.hs_tables_destroy.argtypes = [vp]
@@ -147,9 +148,20 @@ class ParamsSim(HL.HostSim):
         self.L.hs_instance_ticks(self.e, T, HL._p(t))
         return t
 
-    def step(self, T):
-        ns, N, B = self.p.dim_state, self.p.N, self.B
+    def epochs(self):
+        t0, c0 = np.zeros(self.B, np.int32), np.zeros(self.B, np.int32)
+        self.L.hs_epochs_copy(self.e, HL._p(t0), HL._p(c0))
+        return t0, c0
+
+    def ekf_step(self):
         self.L.hs_ekf_step_pp(self.h, self.e, self.t)
+
+    def step(self, T):
+        self.ekf_step()
+        self.update(T)
+
+    def update(self, T):
+        ns, N, B = self.p.dim_state, self.p.N, self.B
         if self.variant == "plain":
             self.L.hs_update_direct_pp(self.h, self.e, self.t, T, HL._p(self.cov))
             return

@@ -14,6 +14,7 @@ from decentralized_ekf_mhe_amd import capi, cassie_params, go1_params, pogox_par
 from decentralized_ekf_mhe_amd.estimator import BatchedEstimator, new_unique_id, streams_host, streams_to_device
 from decentralized_ekf_mhe_amd.streams import make_streams
 from test_gpu_parity import ATOL, RTOL, _params, block_err
+from tworate_lib import schedule as _multirate_schedule
 
 pytestmark = pytest.mark.gpu
 
@@ -103,15 +104,6 @@ def test_pogox_full_batch_1024():
 
 
 # ---------------------------------------------------------------- the reference's two timers together
-def _multirate_schedule(p, B, n_mhe, seed_first=0, **stream_kw):
-    """Sensor events on a 1 ms grid: IMU + joint states every 2 ms (500 Hz, each followed by one EKF timer tick,
-    orien_ekf.cpp:43), the MHE timer every 5 ms (EstSub.cpp:25, parameters_go1.yaml:33), VO as it arrives."""
-    grid = p.copy()
-    grid.rate = 1000
-    n_grid = 5 * (n_mhe - 1) + 1
-    return make_streams(grid, B, n_grid, first_instance=seed_first, **stream_kw), n_grid
-
-
 def _multirate_case(p, B, n_mhe, **stream_kw):
     """both nodes of the reference at their own rates on one event schedule, device against the oracle; returns how many EKF ticks
     replayed history (orien_ekf.cpp:175-205) and the worst replay depth"""

@@ -18,6 +18,7 @@ import pytest
 import direct_lib as DL
 import epoch_lib as EL
 import instance_params_lib as PL
+import tworate_lib as TL
 from decentralized_ekf_mhe_amd import capi
 from decentralized_ekf_mhe_amd.params import DekfParams
 
@@ -167,6 +168,37 @@ def test_restarted_instance_with_a_new_set_is_a_fresh_run_with_that_set(variant)
         EL.assert_life_equal(got, PL.cpu_uniform(name, variant, now[b], T0), b, T0, end, p.N, KEYS, "life")
         assert (got[T0]["status"][b], got[T0]["ticks"][b]) == (capi.DEKF_SOLVE_NONE, 0)
         assert got[end - 1]["status"][b] == capi.DEKF_SOLVE_OK
+
+
+def test_two_rate_restarted_instances_take_another_set():
+    """tworate_lib's event grid and schedule (EKF 500 Hz, MHE 200 Hz: the two epochs of a restart differ) at ekf_history 16, Go1
+    cross, B = 4 on the table SET_OF: every restarted instance takes ANOTHER set at its restart and equals, to the bit, a fresh
+    uniform simulation created with that set and started at the restart's ms; until its first restart an instance is the uniform
+    run with its first set, the untouched instance throughout"""
+    name, H, B, variant = "go1", 16, 4, "cross"
+    p, s, n_grid = TL.streams(name, H, B)
+    set_of = TL.SET_OF[:B]
+    got = TL.run_params_sim(name, H, B, variant, set_of, TL.RESETS, TL.NEW_SETS)
+    for b in range(B):
+        first = min([g for g in TL.RESETS if b in TL.RESETS[g]] + [n_grid])
+        TL.assert_life_equal(got, TL.cpu_fresh(name, H, B, variant, 0, set_of[b]), b, 0, first, p.N, KEYS, "untouched")
+    now = dict(enumerate(set_of))
+    lives = TL.lives(TL.RESETS, n_grid)
+    assert len(lives) == 6 and sum(len(TL.straddling_poses(s, b, g0, g_end)) for b, g0, g_end in lives) >= 1
+    for b, g0, g_end in lives:       # (in the order of the restarts)
+        k = TL.NEW_SETS[g0][b]
+        assert k != now[b]
+        now[b] = k
+        TL.assert_life_equal(got, TL.cpu_fresh(name, H, B, variant, g0, k), b, g0, g_end, p.N, KEYS, "life on set %d" % k)
+        T0 = TL.first_step(g0)
+        assert (got[T0]["t0"][b], got[T0]["c0"][b]) == (T0, TL.ekf_ticks(0, g0)) and got[T0]["c0"][b] != got[T0]["t0"][b]
+        assert (got[T0]["status"][b], got[T0]["ticks"][b]) == (capi.DEKF_SOLVE_NONE, 0)
+        assert got[T0 + TL.steps_of(g0, g_end) - 1]["status"][b] == capi.DEKF_SOLVE_OK
+    assert max(TL.ekf_ticks(g0, g_end) for _, g0, g_end in lives) >= 2 * H
+    # the sets matter on this grid: the life of instance 1 from ms 132 differs from the default set's in x, the quaternion and Cov(x_T)
+    a, c = TL.cpu_fresh(name, H, B, variant, 226, 1), TL.cpu_fresh(name, H, B, variant, 226, 2)
+    for key in ("x", "quat", "cov"):
+        assert not np.array_equal(a[-1][key], c[-1][key]), key
 
 
 # ------------------------------------------------------------------ 5: against the oracle

@@ -15,6 +15,7 @@ import pytest
 
 import direct_lib as DL
 import epoch_lib as EL
+import tworate_lib as TL
 from decentralized_ekf_mhe_amd import capi, go1_params
 
 SYMBOLS = ("dekf_reset_instances", "dekf_get_instance_ticks")
@@ -124,6 +125,49 @@ def test_fold_keeps_the_local_count_modulo_the_history_and_whether_it_is_full():
             assert after % H == local % H and after >= H
 
 
+# ------------------------------------------------------------------ 2b: the two rates (EKF 500 Hz, MHE 200 Hz)
+@pytest.mark.parametrize("name,H", [("go1", 256), ("go1", 16), ("tripod", 16)])
+def test_two_rate_lives_are_fresh_simulations_started_at_their_restart(name, H):
+    """tworate_lib's event grid and schedule, variant cross (which writes every array), B = 4: restarts with EKF ticks behind the last
+    update, with a VO pose that straddles the restart, directly behind an update, inside the instance's own fill on an EKF-tick ms,
+    and of two instances from full windows.  2
+    or 3 EKF ticks lie between two updates, so the two epochs of a restart differ: a core that took one for the other, or the C
+    boundary's order of them, shows here and in no lock-step test.  At ekf_history 16 the rewind ring of a restarted life wraps"""
+    B, variant = 4, "cross"
+    p, s, n_grid = TL.streams(name, H, B)
+    assert (p.ekf_rate, p.rate, p.ekf_history) == (500, 200, H)
+    keys = EL.SIM_KEYS + ("pri_res", "dua_res")
+    got = TL.run_epoch_sim(name, H, B, variant, TL.RESETS)
+    plain = TL.cpu_fresh(name, H, B, variant)
+    assert len(got) == len(plain) == TL.N_MHE
+    assert EL.untouched(TL.RESETS, B) == [3]
+    for b in range(B):
+        first = min([g for g in TL.RESETS if b in TL.RESETS[g]] + [n_grid])
+        TL.assert_life_equal(got, plain, b, 0, first, p.N, keys, "untouched")
+    lives = TL.lives(TL.RESETS, n_grid)
+    assert len(lives) == 6
+    differ, wrapped, straddled = 0, 0, 0
+    for b, g0, g_end in lives:
+        TL.assert_life_equal(got, TL.cpu_fresh(name, H, B, variant, g0), b, g0, g_end, p.N, keys, "life")
+        straddled += len(TL.straddling_poses(s, b, g0, g_end))
+        T0 = TL.first_step(g0)
+        # the epochs the harness holds: the step of the life's first timer event, and the EKF ticks of the handle before ms g0
+        assert (got[T0]["t0"][b], got[T0]["c0"][b]) == (T0, TL.ekf_ticks(0, g0)), (b, g0)
+        assert (got[T0]["status"][b], got[T0]["ticks"][b]) == (capi.DEKF_SOLVE_NONE, 0)
+        assert np.isnan(got[T0]["cov"][b]).all() and not np.isnan(got[T0 + 1]["cov"][b]).any()
+        differ += got[T0]["c0"][b] != got[T0]["t0"][b]
+        wrapped += TL.ekf_ticks(g0, g_end) >= 2 * H
+        # the oracle's filter rewinds inside the life: the restarted instance's ring is read back, never deeper than the ring
+        replays, deepest = TL.oracle_replays(p, s, b, g0, g_end)
+        assert replays >= 1 and deepest < 16, (b, g0, replays, deepest)
+    assert differ == 6
+    assert wrapped >= (3 if H == 16 else 0)
+    assert straddled >= 1      # (the event at which a wrong EKF epoch changes bits: tworate_lib.RESETS)
+    # ms 226 fell behind full windows; ms 132 at instance 1's local step 13: inside its own fill at N = 20, just behind it at N = 12
+    assert got[26]["ticks"][1] == 13 and p.N - 1 <= got[45]["ticks"][0]
+    assert (13 < p.N - 1) == (name == "go1")
+
+
 # ------------------------------------------------------------------ 3: against the oracle
 @pytest.mark.parametrize("b,T0", [(4, 30), (2, 45)])
 def test_life_against_the_oracle_on_the_sliced_log(b, T0):
@@ -230,13 +274,85 @@ static int run(int L, int nj, int N, int steps, int ft, int form) {
     hs_destroy(h);
     return st[0] == 1 && st[1] == 1 && st[2] == 1 && bad == 0 && ticks_ok ? 0 : 2;
 }
-int main() { return run(4, 3, 20, 50, 0, 0) | run(4, 3, 20, 44, 1, 0) | run(2, 5, 6, 30, 1, 1); }
+// The two rates on a 1 ms grid: sensors and one EKF tick on every even ms, the update on every 5th, VO on every 30th from ms 40 on, at a
+// history of 8 samples (the ring wraps in every life).  Instance 1 restarted before ms 63 (an EKF tick lies between the update of ms 60
+// and the restart) and before ms 132 (on an EKF-tick ms, in its own fill), instances 1 and 2 before ms 5 N + 46; instance 0 never
+static int run_two_rate(int L, int nj, int N, int steps, int ft, int form) {
+    dekf_params p; default_params(&p); p.ekf_rate = 500; p.rate = 200; p.ekf_history = 8; p.num_legs = L; p.joints_per_leg = nj; p.N = N; p.leg_odom_type = ft; p.arrival_cost_form = form;
+    const int ns = 9 + 3 * L * ft, B = 3, last = 5 * N + 46;
+    void* h = hs_create(&p, B);
+    if (!h) return 1;
+    void* e = hs_epochs_create(B);
+    std::vector<double> t(B), acc(3 * B), gy(3 * B), pf(3 * L * B), J(3 * L * nj * B), qd(L * nj * B), c(L * B), cov((size_t)B * ns * ns, NAN);
+    std::vector<int> mask(B, 1), ticks(B, 0); std::vector<double> tp(B), tn(B), dp(3 * B), q(4 * B);
+    std::vector<double> xw, cw, l1, zn;
+    int bad = 0;
+    for (int i = 0; i < 5 * (steps - 1) + 1; ++i) {
+        if (i == 63 || i == 132) { const int m[3] = {0, 1, 0}; hs_reset_instances(h, e, m, cov.data()); }
+        if (i == last) { const int m[3] = {0, 1, 1}; hs_reset_instances(h, e, m, cov.data()); }
+        if (i > 39 && i % 30 == 10) {
+            for (int b = 0; b < B; ++b) {
+                tp[b] = 0.001 * (i - 42); tn[b] = 0.001 * (i - 9); dp[3*b] = 0.003; dp[3*b+1] = 0; dp[3*b+2] = 0;
+                q[4*b] = 1; q[4*b+1] = q[4*b+2] = q[4*b+3] = 0;
+            }
+            hs_push_vo(h, mask.data(), tp.data(), tn.data(), dp.data(), tn.data(), q.data());
+        }
+        if (i % 2 == 0) {
+            const int T = i / 5;
+            for (int b = 0; b < B; ++b) {
+                t[b] = 0.001 * i + 1e-5 * b;
+                acc[3*b] = 0.1; acc[3*b+1] = -0.05; acc[3*b+2] = 9.8; gy[3*b] = 0.01; gy[3*b+1] = 0.02; gy[3*b+2] = 0.2;
+                for (int k = 0; k < 3 * L; ++k) pf[3*L*b + k] = 0.1 * (k % 3) - 0.25;
+                for (int k = 0; k < 3 * L * nj; ++k) J[3*L*nj*b + k] = (k % (nj + 1) == 0) ? 0.2 : 0.03 * ((k + T) % 5);
+                for (int k = 0; k < L * nj; ++k) qd[L*nj*b + k] = 0.1 * ((k + T) % 7) - 0.3;
+                for (int k = 0; k < L; ++k) c[L*b + k] = ((T / 5 + k) % 2) ? 1.0 : 0.0;
+            }
+            hs_push_imu(h, t.data(), acc.data(), gy.data());
+            hs_push_leg(h, pf.data(), J.data(), qd.data(), c.data());
+            hs_ekf_step_epoch(h, e);
+        }
+        if (i % 5) continue;
+        const int T = i / 5;
+        xw.assign((size_t)B * N * ns, -7.0);
+        cw.assign((size_t)B * N * ns * ns, -7.0);
+        l1.assign((size_t)B * (N - 1) * ns * ns, -7.0);
+        zn.assign((size_t)B * N * ns * ns, -7.0);
+        hs_update_direct_cross_epoch(h, e, T, cov.data(), xw.data(), cw.data(), l1.data(), zn.data());
+        hs_instance_ticks(e, T, ticks.data());
+        for (int b = 0; b < B; ++b) {
+            const int K = ticks[b] < 1 ? 0 : (ticks[b] + 1 < N ? ticks[b] + 1 : N);
+            for (int k = 0; k < N; ++k) {
+                for (int j = 0; j < ns; ++j) { const double v = xw[((size_t)b * N + k) * ns + j]; bad += k < K ? !std::isfinite(v) : v != -7.0; }
+                for (int j = 0; j < ns * ns; ++j) {
+                    const double v = cw[((size_t)b * N + k) * ns * ns + j], z = zn[((size_t)b * N + k) * ns * ns + j];
+                    bad += k < K ? !std::isfinite(v) : v != -7.0;
+                    bad += k < K ? !std::isfinite(z) : z != -7.0;
+                    if (k < N - 1) { const double w = l1[((size_t)b * (N - 1) + k) * ns * ns + j]; bad += k < K - 1 ? !std::isfinite(w) : w != -7.0; }
+                }
+            }
+            for (int j = 0; j < ns * ns; ++j) bad += K ? !std::isfinite(cov[(size_t)b * ns * ns + j]) : !std::isnan(cov[(size_t)b * ns * ns + j]);
+        }
+    }
+    std::vector<double> x(ns * B); std::vector<int> st(B);
+    hs_get(h, x.data(), nullptr, nullptr, nullptr, st.data(), nullptr, nullptr);
+    std::printf("two rates, L=%d nj=%d N=%d leg_odom_type=%d arrival_cost_form=%d: status %d %d %d ticks %d %d %d, %d bad entries\n", L, nj, N, ft, form,
+                st[0], st[1], st[2], ticks[0], ticks[1], ticks[2], bad);
+    const int T1 = ((last > 132 ? last : 132) + 4) / 5, T2 = (last + 4) / 5;   // (N = 6: ms 132 is instance 1's last restart)
+    const bool ticks_ok = ticks[0] == steps - 1 && ticks[1] == steps - 1 - T1 && ticks[2] == steps - 1 - T2;
+    hs_epochs_destroy(e);
+    hs_destroy(h);
+    return st[0] == 1 && st[1] == 1 && st[2] == 1 && bad == 0 && ticks_ok ? 0 : 2;
+}
+int main() {
+    return run(4, 3, 20, 50, 0, 0) | run(4, 3, 20, 44, 1, 0) | run(2, 5, 6, 30, 1, 1) | run_two_rate(4, 3, 20, 40, 0, 0) | run_two_rate(2, 5, 6, 30, 1, 1);
+}
 """
 
 
 def test_epoch_cores_clean_under_asan_ubsan(tmp_path):
     """a stand-alone program over epoch_hostsim.cpp under AddressSanitizer + UBSan (CPU build, as direct_lib.check_clean_under_asan_ubsan
-    builds its driver): restarts in the window fill and from full windows, Go1 and foot states (both arrival-cost forms)"""
+    builds its driver): restarts in the window fill and from full windows, Go1 and foot states (both arrival-cost forms); and the two
+    rates on a 1 ms grid with restarts that are not aligned with an update, at a history of 8 samples"""
     src = tmp_path / "epoch_driver.cpp"
     src.write_text(ASAN_MAIN)
     exe = tmp_path / "epoch_driver"
