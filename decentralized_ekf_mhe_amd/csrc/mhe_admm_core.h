@@ -384,10 +384,25 @@ DEKF_FN double rows01_from_rows23(double v) {  // [r0 r1 r2 r3] -> [r2 r3 r2 r3]
 // lane_in >= 0: the caller's lane id, read ONCE outside its iteration loop (the three-workgroup kernels' solve loop): the per-lane
 // pointers and strides below are then loop-invariant for the compiler, which may keep them in registers across the iterations —
 // this wavefront's loop holds nothing else.  (Everywhere else the lane id stays opaque at every use, see DEKF_LANE.)
-template <int NF, class Q>
-DEKF_FN void sweeps_one_wave(Q& q, double alpha, int lane_in = -1) {
+// hooks: what the caller weaves into the forward legs (SweepNoHooks: nothing; the three-workgroup kernels: XendsHooks, admm_chunk_r3).
+//   own_x           the caller computes the x columns this wavefront reads first ITSELF instead of finding them in xs:
+//   load()          ... issues their operand loads, in front of every load of the chain;
+//   finish()        ... returns the lane's entry — rows 0 / 1: f_0 / f^_{K-1} (v), rows 2 / 3: the right-hand sides of step 1
+//                   (blocks 1 / K-2; they cross to rows 0 / 1 by v_permlane32_swap) — behind the operand loads of step 1, so that
+//                   those travel during its arithmetic, and has stored the right-hand sides of step 2 (blocks 2 / K-3) to xs;
+//   before_step2()  called between the FMAs of step 1 and the operand prefetch at the top of step 2, the first access to blocks
+//                   3 / K-4 of xs: where the three-workgroup kernels put their barrier "xs complete".  (Needs a step 2: M >= 2.)
+struct SweepNoHooks {
+    static constexpr bool own_x = false;
+    DEKF_FN void load() {}
+    DEKF_FN double finish() { return 0.0; }
+    DEKF_FN void before_step2() {}
+};
+template <int NF, class Q, class H>
+DEKF_FN void sweeps_one_wave(Q& q, double alpha, int lane_in, H& hooks) {
     constexpr int SV = 21 + 3 * Q::LEGS, K = NF, M = mid_block(NF);
     static_assert(NF % 2 == 0 && K - 2 - M == M, "equal forward legs");
+    static_assert(!H::own_x || M >= 2, "before_step2() is called at the top of forward step 2");
     const int lane = lane_in >= 0 ? lane_in : (DEKF_LANE() & 63), row = lane >> 4, li = lane & 15;
     const int i = li < 9 ? li : 8;
     const bool act = li < 9, leg = row < 2, top = (row & 1) == 0;
@@ -397,6 +412,7 @@ DEKF_FN void sweeps_one_wave(Q& q, double alpha, int lane_in = -1) {
     cdptr Dx = Q::R4 ? q.Dxb : q.D;  // inside the full scaling vector (stride SV); R4: the compact LDS copy of the x blocks' entries (D is in the slab)
     constexpr int DST = Q::R4 ? 9 : SV;
     struct Ops { double w[9], rhs; };
+    hooks.load();
     // ---------------- forward: step s = 1..M
     cdptr fm = (leg ? q.Wk : q.Sinv) + ((top ? 0 : (leg ? K - 2 : K - 1)) * 81 + 9 * i);  // block of step 1
     const int fstep = top ? 81 : -81;
@@ -414,15 +430,23 @@ DEKF_FN void sweeps_one_wave(Q& q, double alpha, int lane_in = -1) {
         cdptr W = fm + (s - 1) * fstep;
 #pragma unroll
         for (int t = 0; t < 9; ++t) o.w[t] = W[t];
-        o.rhs = fr[(s - 1) * frstep];
+        // (own_x: blocks 1 / K-2 of xs are not written — the right-hand side of step 1 comes out of hooks.finish() in registers)
+        if (!H::own_x || s != 1) o.rhs = fr[(s - 1) * frstep];
     };
-    double v = xs[(top ? 0 : 9 * (K - 1)) + i];  // f_0 = b_0 / f^_{K-1} = b_{K-1}
+    double v = 0.0;
+    if constexpr (!H::own_x) v = xs[(top ? 0 : 9 * (K - 1)) + i];  // f_0 = b_0 / f^_{K-1} = b_{K-1}
     {
         Ops o[2];
         fload(1, o[0]);
+        if constexpr (H::own_x) {
+            v = hooks.finish();
+            const double r1 = rows01_from_rows23(v);
+            o[0].rhs = leg ? r1 : 0.0;
+        }
 #pragma unroll
         for (int s = 1; s <= M; ++s) {
             const Ops& c = o[(s - 1) & 1];
+            if (s == 2) hooks.before_step2();
             if (s < M) fload(s + 1, o[s & 1]);
             // (letting rows 2, 3 lag one step, so that this cross-row move leaves the dependent path, was
             // measured 1.4 % slower: one more live register and a select per step)
@@ -485,6 +509,11 @@ DEKF_FN void sweeps_one_wave(Q& q, double alpha, int lane_in = -1) {
             xp[s * xstep] = relax(alpha, r, c.xo);
         }
     }
+}
+template <int NF, class Q>
+DEKF_FN void sweeps_one_wave(Q& q, double alpha, int lane_in = -1) {
+    SweepNoHooks none;
+    sweeps_one_wave<NF>(q, alpha, lane_in, none);
 }
 
 // The same one-wavefront, four-row solve for a RUN-TIME (even) window length: the steps are loops, the operands of the next
@@ -1447,9 +1476,19 @@ DEKF_FN void row_tile_finish(Q& q, const RowTile& t, double alpha, double sigma)
 // x-column tiles.  Each side has its own loop with the same sequence of workgroup barriers (s_barrier counts arrivals, it does
 // not care where a wavefront's program counter is), so the 78 state registers are not live in the solve's code and the solve's
 // operand sets are not live in the row code: both fit the 168 VGPRs that three wavefronts per SIMD leave each.
-//   barrier B1: xs complete   (workers: x columns)      ->  wavefront 0: solve
+//   barrier B1: xs complete   (workers: x columns)      ->  wavefront 0: the solve from forward step 2 on
 //   barrier B2: xd complete   (wavefront 0: solve)      ->  workers: rows from registers, w and gb to LDS
-//   barrier B3: w, gb complete (workers)                ->  workers: x columns of the next iteration
+//   barrier B3: w, gb complete (workers)                ->  workers: x columns of the next iteration; wavefront 0: the x columns of
+//                                                           the three blocks at either end, then forward step 1
+// Wavefront 0 does not wait at B1 for the whole x-column phase: the first forward step of its chain reads only the outermost
+// blocks of xs, and those 54 entries it computes itself (XendsHooks; the workers' tiles leave them out), so B1 sits INSIDE the
+// unrolled forward legs, behind step 1 (per iteration on wavefront 0: 475 cycles of waiting from B3 to B1 became 80 at B1 and
+// 220 of work in front of it, profiles/r07_chain_under_xcols_ab.txt).  Every wavefront still passes three barriers per iteration.
+// WRITTEN UNDER THE X PHASE.  Between B3 and B1 wavefront 0 therefore writes while the workers run their x-column tiles (and, in a
+// chunk's first iteration, xcols_regs_load): blocks 2 / K-3 of xs, the zero slot tmp[260 + lane], the dummy slot tmp[176 + lane]
+// and, in forward step 1, -g to blocks 0 / K-1 of xd.  The workers read only at, gb, xb there (plus D and tmp[QSL .. QSL + 9),
+// 162..170, in the load) and write the other blocks of xs: a worker that is given a read of xd, of tmp[176..324) or of the end
+// blocks of xs in that phase races with wavefront 0.
 // One row block's state and constants, by KIND of block — a compile-time parameter, because each worker wavefront runs ONE kind
 // in its own loop (admm_chunk_r3) and must not carry the registers of the others: 0 Meas leg block (equality; 27 doubles),
 // 1 Dyn position / velocity half on a lane pair (equality, 6x6 slack block: + 9 coupling entries), 2 VO / Dyn bias / Meas block on
@@ -1721,11 +1760,13 @@ struct XcolRegs {
     int r[4];     // XKIND 0: rd(kn, a), rv(kn, a), rd(kp, a), rv(kp, a); 1: rm(k, a), rd(kn, 3 + a), rd(kn, a), rd(kp, 3 + a); 2: rd(kn, 6 + a), 3 kn + a (gb), rd(kp, 6 + a)
     double dv, q0;
 };
-template <int XKIND, class Q>
+constexpr int XENDS = 3;  // blocks at either end of the window whose x columns the solve wavefront computes itself (XendsHooks)
+// SKIP_ENDS: the lane owns no entry of those blocks
+template <int XKIND, bool SKIP_ENDS = false, class Q>
 DEKF_FN void xcols_regs_load(const Q& q, int lane, XcolRegs<XKIND>& x) {
     const int K = q.K;
-    x.valid = lane < 3 * K;
-    const int ln = x.valid ? lane : 0;
+    x.valid = lane < 3 * K && !(SKIP_ENDS && (lane < 3 * XENDS || lane >= 3 * (K - XENDS)));
+    const int ln = lane < 3 * K ? lane : 0;
     const int k = ln / 3, a = ln - 3 * k, j = 3 * XKIND + a;
     x.i = 9 * k + j;
     x.hn = k < K - 1; x.hp = k > 0;
@@ -1758,16 +1799,98 @@ DEKF_FN void xcols_regs_tile(Q& q, const XcolRegs<XKIND>& x, double sigma) {
     }
     q.xs[x.i] = fma(x.dv, g, fma(sigma, xv, -x.q0));
 }
+// The x columns of the XENDS outermost blocks at either end of the window, all nine components, on ONE wavefront, laid out the way
+// the first step of sweeps_one_wave wants them (16-lane rows; 54 lanes):
+//   lanes 0..8 of row 0 / 1 / 2 / 3    block 0 / K-1 / 1 / K-2      (f_0, f^_{K-1}; the right-hand sides of step 1)
+//   lanes 9..15 of row 0, 9..10 of 1   block 2, components 0..6, 7..8  (right-hand side of step 2, through xs)
+//   lanes 9..15 of row 2, 9..10 of 3   block K-3, likewise
+// These are the entries the forward legs read before their second step, so the solve wavefront of the three-workgroup kernels
+// computes them itself and starts its chain while the workers are still busy with the other x columns.  A lane's kind is its
+// component / 3; the expressions are those of xcols_regs_tile<kind>, operand for operand: every lane issues the loads of all kinds
+// (the unused ones at at[0]) and keeps its kind's result — no divergent branch; the three forms of the "next" term are ONE fma
+// with a per-lane constant (1: n0 + n1, dt: fma(dt, n1, n0), -1: n0 - n1 — each exactly the sum it replaces).
+struct XendRegs {
+    bool store, hn, hp, k0, k1;  // store: an entry of blocks 2 / K-3, which the chain reads back from xs; k0, k1: kind 0 / kind 1
+    int i;       // entry of xb / xs
+    int r[4];    // kind 0: rd(kn, a), rv(kn, a), rd(kp, a), rv(kp, a); 1: rd(kn, 3 + a), rd(kn, a), rd(kp, 3 + a), -; 2: rd(kn, 6 + a), 3 kn + a (gb), rd(kp, 6 + a), -
+    int rm;      // kind 1: rm(k, a)
+    double cn;   // kind 0: 1, 1: dt, 2: -1
+    double dv, q0;
+};
+template <class Q>
+DEKF_FN void xends_regs_load(const Q& q, int lane, XendRegs& x) {
+    static_assert(XENDS == 3, "the lane map below");
+    const int K = q.K, row = lane >> 4, li = lane & 15;
+    // Only blocks 2 / K-3 go to xs (18 entries): blocks 0 / K-1 and 1 / K-2 reach the chain in registers, and nothing else reads
+    // xs between two x-column phases (the residual checks and the refactorisation do not; the factor-time PA overwrites it).
+    x.store = li >= 9 && ((row & 1) == 0 || li < 11);
+    int k, j;
+    if (li < 9) { j = li; k = row == 0 ? 0 : (row == 1 ? K - 1 : (row == 2 ? 1 : K - 2)); }
+    else { j = x.store ? li - 9 + 7 * (row & 1) : 0; k = row < 2 ? 2 : K - 3; }
+    const int kind = j / 3, a = j - 3 * kind;
+    x.k0 = kind == 0; x.k1 = kind == 1;
+    x.i = 9 * k + j;
+    x.hn = k < K - 1; x.hp = k > 0;
+    const int kn = x.hn ? k : 0, kp = x.hp ? k - 1 : 0;
+    x.rm = 0;
+    if (kind == 0) { x.r[0] = q.ix.rd(kn, a); x.r[1] = q.ix.rv(kn, a); x.r[2] = q.ix.rd(kp, a); x.r[3] = q.ix.rv(kp, a); x.cn = 1.0; }
+    else if (kind == 1) { x.rm = q.ix.rm(k, a); x.r[0] = q.ix.rd(kn, 3 + a); x.r[1] = q.ix.rd(kn, a); x.r[2] = q.ix.rd(kp, 3 + a); x.r[3] = 0; x.cn = q.c.dt; }
+    else { x.r[0] = q.ix.rd(kn, 6 + a); x.r[1] = 3 * kn + a; x.r[2] = q.ix.rd(kp, 6 + a); x.r[3] = 0; x.cn = -1.0; }
+    x.dv = q.D[k * (21 + 3 * Q::LEGS) + j];
+    const double qv = (q.tmp + TmpMap<9>::QSL)[j];
+    x.q0 = k == 0 ? qv : 0.0;
+}
+// what admm_chunk_r3 weaves into the forward legs of sweeps_one_wave (see there)
+template <class Q>
+struct XendsHooks {
+    static constexpr bool own_x = true;
+    Q& q;
+    const XendRegs& x;
+    double sigma;
+    double xv, a0, a1, a2, a3, m[Q::LEGS];
+    long long tb;  // -DDEKF_PROFILE_TL: cycles spent at the barrier
+    DEKF_FN XendsHooks(Q& q_, const XendRegs& x_, double sigma_) : q(q_), x(x_), sigma(sigma_), tb(0) {}
+    DEKF_FN void load() {
+        cdptr at = q.at;
+        cdptr s1 = x.k0 || x.k1 ? at : cdptr(q.gb);
+        xv = q.xb[x.i];
+#pragma unroll
+        for (int leg = 0; leg < Q::LEGS; ++leg) m[leg] = at[x.rm + 3 * leg];
+        a0 = at[x.r[0]]; a1 = s1[x.r[1]]; a2 = at[x.r[2]]; a3 = at[x.r[3]];
+    }
+    DEKF_FN double finish() {
+        double gm = 0.0;
+#pragma unroll
+        for (int leg = 0; leg < Q::LEGS; ++leg) gm += m[leg];
+        const double nx = fma(x.cn, a1, a0), ps = a2 + a3;
+        const double n = x.hn ? nx : 0.0, pv = x.k0 ? ps : a2, p = x.hp ? pv : 0.0;
+        const double gn = gm + n;
+        const double g = (x.k1 ? gn : n) - p;
+        const double val = fma(x.dv, g, fma(sigma, xv, -x.q0));
+        if (x.store) q.xs[x.i] = val;
+        return val;
+    }
+    DEKF_FN void before_step2() {
+#if defined(DEKF_PROFILE_TL)
+        const long long ta = clock64();
+#endif
+        DEKF_SYNC();  // B1
+#if defined(DEKF_PROFILE_TL)
+        tb = clock64() - ta;
+#endif
+    }
+};
 template <int NF, class Q>
 DEKF_FN void admm_chunk_r3(Q& q, int iters, double alpha, double sigma) {
     constexpr int L = Q::LEGS, SV = 21 + 3 * L;
     static_assert(3 * NF <= 64 && 2 * (NF - 1) <= 64, "one tile per kind");
+    static_assert(NF >= 2 * XENDS && mid_block(NF) >= 2, "the solve wavefront's own x columns are distinct blocks and step 1 reads no others");
     static_assert(NF * L <= 64 || (NF * L - 64) + 2 * (NF - 1) <= 64, "the Meas blocks beyond 64 fit the VO / bias wavefront");
     const int w = __builtin_amdgcn_readfirstlane(DEKF_LANE() >> 6), lane = DEKF_LANE() & 63;
     // (the x blocks stay in LDS, q.xb, for the whole solve)
     // -DDEKF_PROFILE -DDEKF_PROFILE_TL: per-wavefront intervals, summed over the iterations (tools/profile_sections.py, DEKF_TIMELINE=1)
-    //   prof[w]: w0 the solve, workers the x-column tile | prof[4 + w]: w0 its wait from B2 to B1, workers the row tile |
-    //   prof[8 + w]: workers' wait for the solve (B1 to B2)
+    //   prof[w]: w0 its own x columns and the solve, workers the x-column tile | prof[4 + w]: w0 its wait from B2 to B3, workers the row tile |
+    //   prof[8 + w]: w0 its wait at B1 (inside the chain), workers' wait for the solve (B1 to B2)
 #if defined(DEKF_PROFILE_TL)
 #define DEKF_R3_T(var) const long long var = clock64()
 #else
@@ -1776,23 +1899,28 @@ DEKF_FN void admm_chunk_r3(Q& q, int iters, double alpha, double sigma) {
     if (w == 0) {
         DEKF_SYNC();  // B0: w, gb of the (re)start complete
         DEKF_PROF_MARK(q, 14);
+        // The chain starts UNDER the workers' x-column phase: this wavefront computes the x columns of the three outermost blocks
+        // at either end itself (all that forward step 1 and the prefetch at its top read), and meets the workers at B1 only
+        // between step 1 and the prefetch of step 2 (the workers' tiles leave those 54 entries out: one owner per entry).
+        XendRegs xe;
+        xends_regs_load(q, lane, xe);
+        XendsHooks<Q> hooks(q, xe, sigma);
         for (int it = 0; it < iters; ++it) {
             DEKF_R3_T(t0);
-            DEKF_SYNC();  // B1
-            DEKF_R3_T(t1);
             __builtin_amdgcn_s_setprio(3);
-            sweeps_one_wave<NF>(q, alpha, lane);
+            sweeps_one_wave<NF>(q, alpha, lane, hooks);
             __builtin_amdgcn_s_setprio(0);
 #if defined(DEKF_PROFILE_TL)
             __builtin_amdgcn_s_waitcnt(0);
+            const long long tb = hooks.tb;
 #endif
             DEKF_R3_T(t2);
             DEKF_SYNC();  // B2
             DEKF_SYNC();  // B3
             DEKF_R3_T(t3);
-            DEKF_TL_ADD(q, 0, t1, t2);
+            DEKF_TL_ADD(q, 0, t0 + tb, t2);  // (its own x columns and the solve, without the wait at B1)
             DEKF_TL_ADD(q, 4, t2, t3);
-            DEKF_TL_ADD(q, 8, t0, t1);
+            DEKF_TL_ADD(q, 8, 0LL, tb);
         }
     } else {
         // one loop per kind of row block (wave-uniform branch): each is compiled with the registers of ITS block kind only
@@ -1804,7 +1932,7 @@ DEKF_FN void admm_chunk_r3(Q& q, int iters, double alpha, double sigma) {
             constexpr int xkind = KIND == 0 ? 1 : (KIND == 1 ? 2 : 0);  // velocity columns (the longest gather) next to the shortest row tile
             const bool cold = q.cold;
             XcolRegs<xkind> xc;
-            xcols_regs_load<xkind>(q, lane, xc);
+            xcols_regs_load<xkind, true>(q, lane, xc);  // (without the end blocks: the solve wavefront's)
             for (int it = 0; it < iters; ++it) {
                 DEKF_R3_T(t0);
                 xcols_regs_tile<xkind>(q, xc, sigma);

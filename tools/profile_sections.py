@@ -64,8 +64,12 @@ def main():
         # fixed-horizon iteration, summed over the iterations of the last solve
         it = float(info["iters"].mean())
         print(f"iterations {it:.1f}; cycles per iteration and wavefront (w0 runs the solve)")
-        for name, base in (("solve | tile prefetch, up to the barrier", 0), ("row-tile work behind the barrier", 4),
-                           ("wait at the barrier that ends the row phase", 8)):
+        rows = (("solve | tile prefetch, up to the barrier", 0), ("row-tile work behind the barrier", 4),
+                ("wait at the barrier that ends the row phase", 8))
+        if "_r3_" in est.solve_kernel_name(True):  # admm_chunk_r3's slots: wavefront 0 | the workers
+            rows = (("w0: own x columns + solve (less B1) | x tile", 0), ("w0: wait B2..B3 | row tile", 4),
+                    ("w0: wait at B1, inside the chain | B1..B2", 8))
+        for name, base in rows:
             print(f"  {name:46s}" + "".join(f"  w{w}: {mean[base + w] / it:7.0f}" for w in range(4)))
         print(json.dumps({"batch": B, "T": K - 1, "mean_iters": it, "per_iteration_cycles": {
             "to_barrier": [mean[w] / it for w in range(4)], "row_work": [mean[4 + w] / it for w in range(4)],
