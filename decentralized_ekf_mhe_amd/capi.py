@@ -58,7 +58,9 @@ PROTOTYPES = {
     "dekf_get_instance_ticks": (C.c_int, [_vp, _vp, C.c_int]),
     "dekf_set_instance_params": (C.c_int, [_vp, _vp, C.c_int, _vp]),
     "dekf_get_instance_params": (C.c_int, [_vp, C.c_int, C.POINTER(DekfParams)]),
-    "dekf_timing_enable": (C.c_int, [_vp, C.c_int]),
+    "dekf_set_active": (C.c_int, [_vp, _vp, C.c_int]),
+    "dekf_get_active": (C.c_int, [_vp, _vp, C.c_int]),
+    "dekf_timing_enable":(C.c_int, [_vp, C.c_int]),
     "dekf_timing_read": (C.c_int, [_vp, _dp, _ip]),
     "dekf_launch_info": (C.c_int, [_vp, _ip, _ip, _dp]),
     "dekf_solve_kernel_name": (C.c_char_p, [_vp, C.c_int]),

@@ -15,6 +15,7 @@
 #include "mhe_direct_core.h"
 #include "mhe_epoch_core.h"
 #include "mhe_params_core.h"
+#include "mhe_pause_core.h"
 #include "mhe_solve_core.h"
 
 using namespace dekf;
@@ -62,6 +63,14 @@ __global__ void k_mhe_marginalize_early_pp(DevState s, int T, const int* t0, con
 __global__ void k_reset_instances_pp(DevCfg c, DevState s, const int* mask, double* cov, int* t0, int* c0, int next_T, int ekf_count, const double* pe);
 __global__ void k_reset_state_pp(DevCfg c, DevState s, const double* pe);
 __global__ void k_ekf_init_pp(DevCfg c, DevState s, const int* mask, const double* pe);
+// pausing single instances (mhe_pause_core.h)
+__global__ void k_ekf_tick_act(DevCfg c, DevState s, int count, const int* c0);
+__global__ void k_ekf_tick_act_pp(DevCfg c, DevState s, int count, const int* c0, const double* pe);
+__global__ void k_mhe_assemble_act(DevCfg c, DevState s, int T, int pushes, const int* t0);
+__global__ void k_mhe_assemble_act_pp(DevState s, int T, int pushes, const int* t0, const DevCfg* pc);
+__global__ void k_latch_vo_act(DevCfg c, DevState s, const int* mask, const int* t0, const double* t_pre, const double* t_now,
+                               const double* dp, const double* t_pose, const double* q_vo);
+__global__ void k_fold_epochs_act(int* c0, int B, int count_old, int count_new, int H);
 __global__ void k_ekf_cov_out(DevCfg c, DevState s, double* out);
 __global__ void k_latch4(LatchCopy4 a);
 __global__ void k_go1_leg_odometry(DevCfg c, DevState s, const double* jp, const double* jv, const double* force,
@@ -124,6 +133,14 @@ struct dekf_handle_s {
     std::vector<int> t0_host, c0_host;
     int min_t0 = 0;
     bool epochs = false;
+    // dekf_set_active: pausing single instances (mhe_pause_core.h).  While instance b is paused the device's t0[b] and c0[b], and
+    // t0_host[b] and c0_host[b] with them, hold the sentinel, and pz_step[b] | pz_count[b] its next local step and local EKF count;
+    // act_host[b]: 1 runs, 0 is paused (all three allocated with the epochs).  min_t0 is then the smallest epoch of the active
+    // instances (the sentinel: none is) and max_frozen the largest local step at which a paused one stands (-1: none is paused).
+    // pausing: an instance has been paused since dekf_create / dekf_reset — the handle launches the *_act kernels, which skip one
+    std::vector<int> act_host, pz_step, pz_count;
+    int max_frozen = -1;
+    bool pausing = false;
     // dekf_set_instance_params: the noise constants of every instance of a direct handle (mhe_params_core.h).  pp_mhe [B] DevCfg
     // and pp_ekf [PpEkf::len][B] on the device, allocated by the first call that sets a table; inst_prm: the handle's parameters with
     // every instance's noise fields (dekf_get_instance_params).  pp: the handle has a table: it launches the *_pp kernels, which are
@@ -451,8 +468,22 @@ dekf_status ensure_epochs(dekf_handle h) {
     h->ep_c0 = e + B;
     h->t0_host.assign(B, 0);
     h->c0_host.assign(B, 0);
+    h->act_host.assign(B, 1);
+    h->pz_step.assign(B, 0);
+    h->pz_count.assign(B, 0);
     h->min_t0 = 0;
+    h->max_frozen = -1;
     return DEKF_OK;
+}
+
+// what the window getters' steps take from the epochs: the smallest one of the active instances, the largest frozen local step
+void epoch_bounds(dekf_handle h) {
+    h->min_t0 = DEKF_EPOCH_PAUSED;
+    h->max_frozen = -1;
+    for (size_t b = 0; b < h->t0_host.size(); ++b) {
+        if (h->act_host[b]) { if (h->t0_host[b] < h->min_t0) h->min_t0 = h->t0_host[b]; }
+        else if (h->pz_step[b] - 1 > h->max_frozen) h->max_frozen = h->pz_step[b] - 1;
+    }
 }
 
 struct Timed {  // brackets one launch with events when timing is on
@@ -498,7 +529,9 @@ dekf_status assemble_step(dekf_handle h, const MheStep& st) {
     if (h->early_pending) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_early_done, 0)); h->early_pending = false; }
     {
         Timed t(h, 1);
-        if (h->pp) k_mhe_assemble_pp<<<h->c.B, 64, h->lds_asm, h->stream>>>(st.sp, st.T, h->pushes, h->ep_t0, h->pp_mhe);
+        if (h->pausing && h->pp) k_mhe_assemble_act_pp<<<h->c.B, 64, h->lds_asm, h->stream>>>(st.sp, st.T, h->pushes, h->ep_t0, h->pp_mhe);
+        else if (h->pausing) k_mhe_assemble_act<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->c, st.sp, st.T, h->pushes, h->ep_t0);
+        else if (h->pp) k_mhe_assemble_pp<<<h->c.B, 64, h->lds_asm, h->stream>>>(st.sp, st.T, h->pushes, h->ep_t0, h->pp_mhe);
         else if (h->epochs) k_mhe_assemble_ep<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->c, st.sp, st.T, h->pushes, h->ep_t0);
         else k_mhe_assemble<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->c, st.sp, st.T, h->pushes);
     }
@@ -560,8 +593,9 @@ dekf_status solve_step(dekf_handle h, const MheStep& st) {
     h->last_par = par;
     h->mhe_cov_valid = h->solver == DEKF_SOLVER_DIRECT;
     h->win_steps = h->smoother ? K : 0;
-    if (h->epochs && h->smoother) {  // the largest window of the batch: the instance restarted longest ago (none at its local step 0)
-        const int Tl = T - h->min_t0;
+    if (h->epochs && h->smoother) {  // the largest window of the batch: the instance restarted longest ago (none at its local step 0),
+        const int Ta = T - h->min_t0;  // or a paused one with the window it stands at
+        const int Tl = Ta > h->max_frozen ? Ta : h->max_frozen;
         h->win_steps = Tl < 1 ? 0 : (Tl + 1 < h->c.N ? Tl + 1 : h->c.N);
     }
     return DEKF_OK;
@@ -794,8 +828,10 @@ dekf_status dekf_reset(dekf_handle h) {
         HIPCHK(hipMemsetAsync(h->ep_t0, 0, 2 * (size_t)h->c.B * sizeof(int), h->stream));
         h->t0_host.assign((size_t)h->c.B, 0);
         h->c0_host.assign((size_t)h->c.B, 0);
+        h->act_host.assign((size_t)h->c.B, 1);  // (pausing is state, not a setting: a reset handle is a fresh handle)
         h->min_t0 = 0;
-        h->epochs = false;
+        h->max_frozen = -1;
+        h->epochs = h->pausing = false;
     }
     return DEKF_OK;
 }
@@ -835,11 +871,9 @@ dekf_status dekf_reset_instances(dekf_handle h, const int* mask, dekf_mem where)
     else k_reset_instances<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->s, dmask, h->mhe_cov, h->ep_t0, h->ep_c0, h->next_T, h->ekf_count);
     HIPCHK(hipGetLastError());
     if (where == DEKF_HOST) HIPCHK(hipStreamSynchronize(h->stream));  // (m, a local, is the source of the copy)
-    h->min_t0 = h->next_T;
-    for (size_t b = 0; b < B; ++b) {
-        if (m[b]) { h->t0_host[b] = h->next_T; h->c0_host[b] = h->ekf_count; }
-        if (h->t0_host[b] < h->min_t0) h->min_t0 = h->t0_host[b];
-    }
+    for (size_t b = 0; b < B; ++b)  // (a paused instance that is restarted is active: its new life starts here)
+        if (m[b]) restart_instance((int)b, h->act_host.data(), h->t0_host.data(), h->c0_host.data(), h->next_T, h->ekf_count);
+    epoch_bounds(h);
     h->epochs = true;
     return DEKF_OK;
 }
@@ -851,12 +885,63 @@ dekf_status dekf_get_instance_ticks(dekf_handle h, int* ticks, dekf_mem where) {
     const int T = h->next_T - 1;  // the step of the last update (0: dekf_initialize)
     std::vector<int> t(B, T);
     if (h->epochs)
-        for (size_t b = 0; b < B; ++b) t[b] = T - h->t0_host[b];
+        for (size_t b = 0; b < B; ++b) t[b] = instance_tick((int)b, T, h->act_host.data(), h->pz_step.data(), h->t0_host.data());
     if (where == DEKF_HOST) std::memcpy(ticks, t.data(), B * sizeof(int));
     else {
         HIPCHK(hipSetDevice(h->device));
         HIPCHK(hipMemcpyAsync(ticks, t.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));  // (t is a local)
+    }
+    return DEKF_OK;
+}
+
+dekf_status dekf_set_active(dekf_handle h, const int* active, dekf_mem where) {
+    if (!h) return fail(DEKF_ERR_INVALID, "null handle");
+    if (!active) return fail(DEKF_ERR_INVALID, "null mask");
+    if (h->c.est_type != 0) return fail(DEKF_ERR_INVALID, "dekf_set_active needs a direct MHE handle: this is a KF handle (est_type 1)");
+    if (h->pipelined) return fail(DEKF_ERR_INVALID, "dekf_set_active cannot be combined with solve_pipeline = 1");
+    if (h->solver != DEKF_SOLVER_DIRECT) return fail(DEKF_ERR_INVALID, "dekf_set_active needs a direct handle (dekf_set_solver(h, DEKF_SOLVER_DIRECT))");
+    if (!h->initialized) return fail(DEKF_ERR_ORDER, "dekf_set_active before dekf_initialize");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t B = (size_t)h->c.B;
+    // the host reads the mask, as dekf_reset_instances does: it refuses values other than 0 and 1 and keeps the books of the pauses
+    std::vector<int> m(B);
+    if (where == DEKF_HOST) std::memcpy(m.data(), active, B * sizeof(int));
+    else {
+        HIPCHK(hipMemcpyAsync(m.data(), active, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    bool change = false;
+    for (size_t b = 0; b < B; ++b) {
+        if (m[b] != 0 && m[b] != 1) return fail(DEKF_ERR_INVALID, "dekf_set_active: mask entries must be 0 or 1");
+        change = change || m[b] != (h->ep_t0 ? h->act_host[b] : 1);
+    }
+    if (!change) return DEKF_OK;  // the mask the handle has: nothing changes, the kernels it launches included
+    TRY(quiesce(h));  // (what dekf_reset_instances waits for: the arrival cost computed ahead reads the epochs)
+    TRY(ensure_epochs(h));
+    for (size_t b = 0; b < B; ++b)
+        set_active_instance((int)b, m[b], h->act_host.data(), h->pz_step.data(), h->pz_count.data(), h->t0_host.data(), h->c0_host.data(),
+                            h->next_T, h->ekf_count, h->c.ekf_hist);
+    HIPCHK(hipMemcpyAsync(h->ep_t0, h->t0_host.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->ep_c0, h->c0_host.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));  // (the host's copies change at the next call)
+    epoch_bounds(h);
+    h->epochs = true;
+    h->pausing = true;  // (a change on a handle that has paused nobody is a pause)
+    return DEKF_OK;
+}
+
+dekf_status dekf_get_active(dekf_handle h, int* active, dekf_mem where) {
+    if (!h || !active) return fail(DEKF_ERR_INVALID, "null argument");
+    if (!h->initialized) return fail(DEKF_ERR_ORDER, "dekf_get_active before dekf_initialize");
+    const size_t B = (size_t)h->c.B;
+    std::vector<int> a(B, 1);
+    if (h->pausing) a = h->act_host;
+    if (where == DEKF_HOST) std::memcpy(active, a.data(), B * sizeof(int));
+    else {
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipMemcpyAsync(active, a.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));  // (a is a local)
     }
     return DEKF_OK;
 }
@@ -898,8 +983,11 @@ dekf_status dekf_set_instance_params(dekf_handle h, const dekf_params* sets, int
         for (size_t b = 0; b < B; ++b) {
             if (set_of[b] < 0) continue;
             // only an instance that dekf_reset_instances has restarted and that has seen neither an update nor an EKF tick since:
-            // its own local step is -1 and its own local EKF count 0, whatever the handle ticked before the restart
-            const bool restarted = h->initialized && h->epochs && T - h->t0_host[b] == -1 && h->ekf_count == h->c0_host[b];
+            // its own local step is -1 and its own local EKF count 0, whatever the handle ticked before the restart (or ticks
+            // while the instance is paused: mhe_pause_core.h)
+            const bool restarted = h->initialized && h->epochs &&
+                                   instance_tick((int)b, T, h->act_host.data(), h->pz_step.data(), h->t0_host.data()) == -1 &&
+                                   instance_count((int)b, h->ekf_count, h->act_host.data(), h->pz_count.data(), h->c0_host.data()) == 0;
             if (!restarted)
                 return fail(DEKF_ERR_ORDER, "dekf_set_instance_params: an instance takes a set before its first tick only (before the first "
                                             "dekf_ekf_step, right after dekf_reset, or right after dekf_reset_instances restarted it)");
@@ -1015,7 +1103,8 @@ dekf_status dekf_push_vo(dekf_handle h, const int* mask, const double* t_pre, co
             TRY(stage_in(h, 6 * B * 8, &q_vo, 4 * B));
         }
     }
-    k_latch_vo<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->s, mask, t_pre, t_now, dp_body, t_pose, q_vo);
+    if (h->pausing) k_latch_vo_act<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->s, mask, h->ep_t0, t_pre, t_now, dp_body, t_pose, q_vo);
+    else k_latch_vo<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->s, mask, t_pre, t_now, dp_body, t_pose, q_vo);
     HIPCHK(hipGetLastError());
     return DEKF_OK;
 }
@@ -1029,7 +1118,9 @@ dekf_status dekf_ekf_step(dekf_handle h) {
     if (!h) return fail(DEKF_ERR_INVALID, "null handle");
     {
         Timed t(h, 0);
-        if (h->pp) k_ekf_tick_pp<<<(h->c.B + 63) / 64, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count, h->ep_c0, h->pp_ekf);
+        if (h->pausing && h->pp) k_ekf_tick_act_pp<<<(h->c.B + 63) / 64, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count, h->ep_c0, h->pp_ekf);
+        else if (h->pausing) k_ekf_tick_act<<<(h->c.B + 63) / 64, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count, h->ep_c0);
+        else if (h->pp) k_ekf_tick_pp<<<(h->c.B + 63) / 64, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count, h->ep_c0, h->pp_ekf);
         else if (h->epochs) k_ekf_tick_ep<<<(h->c.B + 63) / 64, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count, h->ep_c0);
         else k_ekf_tick<<<(h->c.B + 63) / 64, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count);
     }
@@ -1041,10 +1132,12 @@ dekf_status dekf_ekf_step(dekf_handle h) {
         const int folded = h->c.ekf_hist + h->ekf_count % h->c.ekf_hist;
         // A restarted instance's tick runs on its local count, ekf_count - c0[b]: every epoch is moved so that the local count keeps
         // its value modulo the ring depth and whether it has reached it (mhe_epoch_core.h: fold_epoch).  An epoch of 0 stays 0.
+        // A paused instance's epoch is the sentinel and stays it; its stored local count needs no fold (mhe_pause_core.h).
         if (h->epochs) {
-            k_fold_epochs<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->ep_c0, h->c.B, h->ekf_count, folded, h->c.ekf_hist);
+            if (h->pausing) k_fold_epochs_act<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->ep_c0, h->c.B, h->ekf_count, folded, h->c.ekf_hist);
+            else k_fold_epochs<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->ep_c0, h->c.B, h->ekf_count, folded, h->c.ekf_hist);
             HIPCHK(hipGetLastError());
-            for (int& c0 : h->c0_host) c0 = fold_epoch(c0, h->ekf_count, folded, h->c.ekf_hist);  // (the host's copy moves alike)
+            for (int& c0 : h->c0_host) c0 = fold_epoch_active(c0, h->ekf_count, folded, h->c.ekf_hist);  // (the host's copy moves alike)
         }
         h->ekf_count = folded;
     }
@@ -1074,6 +1167,7 @@ dekf_status dekf_update(dekf_handle h, int T) {
     if (!h) return fail(DEKF_ERR_INVALID, "null handle");
     if (!h->initialized) return fail(DEKF_ERR_ORDER, "dekf_update before dekf_initialize");
     if (T != h->next_T) return fail(DEKF_ERR_ORDER, "update(T) must be called with T = 1, 2, 3, ... (EstSub.cpp:58-75)");
+    if (h->pausing && T >= DEKF_EPOCH_PAUSED) return fail(DEKF_ERR_ORDER, "a handle that has paused an instance runs 2^31 - 2^16 steps: dekf_reset it");
     if (h->c.est_type == 0) {
         // the terms, the solve behind them (pipelined: on its own stream), in-order: the next step's arrival cost beside the solve
         const MheStep st = mhe_step(h, T);

@@ -12,6 +12,7 @@
 //   k_latch4          device-to-device sensor latch of one push (IMU or leg arrays) in one launch
 //   k_reset_instances, k_*_ep   restarting single instances of a direct handle (dekf_reset_instances, mhe_epoch_core.h)
 //   k_*_pp            the same with noise parameters per instance (dekf_set_instance_params, mhe_params_core.h)
+//   k_*_act           the tick, assemble, VO latch and fold of a handle that has paused an instance (dekf_set_active, mhe_pause_core.h)
 #include <hip/hip_runtime.h>
 
 #include "cfg.h"
@@ -22,6 +23,7 @@
 #include "mhe_direct_core.h"
 #include "mhe_epoch_core.h"
 #include "mhe_params_core.h"
+#include "mhe_pause_core.h"
 #include "mhe_solve_core.h"
 
 using namespace dekf;
@@ -179,6 +181,28 @@ __global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_marginalize_early_pp
                                                                                  const DevCfg* __restrict__ pc) {
     extern __shared__ double lds[];
     marginalize_early_pp(pc, s, blockIdx.x, T, t0, lds);
+}
+
+// A direct handle that has paused an instance (dekf_set_active) launches these in place of k_ekf_tick_ep and k_mhe_assemble_ep, or of
+// k_ekf_tick_pp and k_mhe_assemble_pp where it has a parameter table: the same cores, or nothing for an instance whose epoch is the
+// sentinel (mhe_pause_core.h; in the assemble kernels one scalar load per workgroup).  The marginalise and solve kernels of such a
+// handle are the epoch and parameter twins as they are: they do nothing below a local step of 2 and of 1.
+__global__ void __launch_bounds__(64) k_ekf_tick_act(DevCfg c, DevState s, int count, const int* c0) {
+    int b = blockIdx.x * 64 + threadIdx.x;
+    if (b < c.B) ekf_tick_active(c, s, b, count, c0);
+}
+__global__ void __launch_bounds__(64) k_ekf_tick_act_pp(DevCfg c, DevState s, int count, const int* c0, const double* __restrict__ pe) {
+    int b = blockIdx.x * 64 + threadIdx.x;
+    if (b < c.B) ekf_tick_active_pp(c, s, b, count, c0, pe);
+}
+__global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_assemble_act(DevCfg c, DevState s, int T, int pushes, const int* t0) {
+    extern __shared__ double lds[];
+    assemble_active(c, s, blockIdx.x, T, pushes, t0, lds);
+}
+__global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_assemble_act_pp(DevState s, int T, int pushes, const int* t0,
+                                                                            const DevCfg* __restrict__ pc) {
+    extern __shared__ double lds[];
+    assemble_active_pp(pc, s, blockIdx.x, T, pushes, t0, lds);
 }
 #endif  // DEKF_MISC_KERNELS
 
@@ -346,6 +370,14 @@ __global__ void k_latch_vo(DevCfg c, DevState s, const int* mask, const double* 
     }
 }
 
+// k_latch_vo of a handle that has paused an instance: a sample for a paused instance is dropped (mhe_pause_core.h).  t0: the epochs
+__global__ void k_latch_vo_act(DevCfg c, DevState s, const int* mask, const int* t0, const double* t_pre, const double* t_now,
+                               const double* dp, const double* t_pose, const double* q_vo) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= c.B || !mask[b]) return;
+    latch_vo_active(s, b, t0, t_pre, t_now, dp, t_pose, q_vo);
+}
+
 // the device-pointer form of dekf_push_imu / dekf_push_leg: all arrays of one push in one grid-stride copy
 __global__ void __launch_bounds__(256) k_latch4(LatchCopy4 a) {
     const size_t total = a.end[3], stride = (size_t)gridDim.x * blockDim.x;
@@ -384,6 +416,11 @@ __global__ void k_reset_instances(DevCfg c, DevState s, const int* mask, double*
 __global__ void k_fold_epochs(int* c0, int B, int count_old, int count_new, int H) {
     int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < B) c0[b] = fold_epoch(c0[b], count_old, count_new, H);
+}
+// the same on a handle that has paused an instance: the sentinel of a paused one stays (fold_epoch_active)
+__global__ void k_fold_epochs_act(int* c0, int B, int count_old, int count_new, int H) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) c0[b] = fold_epoch_active(c0[b], count_old, count_new, H);
 }
 
 // dekf_reset_instances and dekf_reset of a handle with a parameter table: every instance's own initial EKF state (mhe_params_core.h);

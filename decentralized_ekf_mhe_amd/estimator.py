@@ -165,10 +165,24 @@ class BatchedEstimator:
 
     def instance_ticks(self):
         """int32 [B]: the local step of every instance at the last update (dekf_get_instance_ticks): T, or T - T0 for an instance
-        restarted before step T0; its window then holds min(ticks + 1, N) steps"""
+        restarted before step T0; its window then holds min(ticks + 1, N) steps.  Frozen while an instance is paused (set_active)"""
         t = np.zeros(self.batch, np.int32)
         capi.check(self.lib.dekf_get_instance_ticks(self.h, C.c_void_p(t.ctypes.data), capi.DEKF_HOST))
         return t
+
+    def set_active(self, mask):
+        """pause the instances whose mask entry is 0 and resume those whose entry is 1 (dekf_set_active; a direct handle, between
+        update(T - 1) and update(T)): a paused instance stands still, every getter keeps its bits, and it goes on where it stopped
+        once it is resumed.  The call states the whole mask.  mask: int32 [B], numpy or a torch CUDA tensor (which must be complete on
+        its stream)"""
+        p, w = _ptr_where(mask, np.int32)
+        capi.check(self.lib.dekf_set_active(self.h, p, w))
+
+    def active(self):
+        """int32 [B]: 1 for an instance that runs, 0 for a paused one (dekf_get_active)"""
+        a = np.zeros(self.batch, np.int32)
+        capi.check(self.lib.dekf_get_active(self.h, C.c_void_p(a.ctypes.data), capi.DEKF_HOST))
+        return a
 
     def set_instance_params(self, sets, set_of):
         """noise parameters per instance of a direct handle (dekf_set_instance_params): sets, a sequence of DekfParams that differ from

@@ -371,8 +371,8 @@ dekf_status dekf_get_window_cross(dekf_handle h, int* steps, double* cov_lag1, d
  * dekf_get_instance_ticks(h, ticks, where): ticks[B], the local step of every instance at the last update: T on a handle that never
  * restarted one, T - T0 after a restart before step T0 (-1 between the restart and dekf_update(h, T0)); K_b = min(ticks[b] + 1, N)
  * once ticks[b] >= 1.  Any initialised handle; DEKF_ERR_ORDER before dekf_initialize, DEKF_ERR_INVALID for a null handle or pointer.
- * Not part of this interface: ADMM handles (their launch takes one window length for the batch), KF and pipelined handles, instances
- * that are switched off.  (Parameters per instance: dekf_set_instance_params below.) */
+ * Not part of this interface: ADMM handles (their launch takes one window length for the batch), KF and pipelined handles.
+ * (Parameters per instance: dekf_set_instance_params below; instances that are switched off: dekf_set_active below.) */
 dekf_status dekf_reset_instances(dekf_handle h, const int* mask, dekf_mem where);
 dekf_status dekf_get_instance_ticks(dekf_handle h, int* ticks, dekf_mem where);
 
@@ -413,9 +413,53 @@ dekf_status dekf_get_instance_ticks(dekf_handle h, int* ticks, dekf_mem where);
  * dekf_get_instance_params(h, b, out): the handle's parameters with instance b's noise fields; on any handle (without a table: the
  * handle's own parameters).  DEKF_ERR_INVALID for b outside 0 .. B - 1 or a null pointer.
  * Not part of this interface: ADMM, KF and pipelined handles; structure, rates, horizon, solver settings, contact_effort_threshold
- * or the IMU-to-body transform per instance; instances that are switched off. */
+ * or the IMU-to-body transform per instance.  (Instances that are switched off: dekf_set_active below.) */
 dekf_status dekf_set_instance_params(dekf_handle h, const dekf_params* sets, int nsets, const int* set_of);
 dekf_status dekf_get_instance_params(dekf_handle h, int b, dekf_params* out);
+
+/* ---- pausing single instances (direct handles): one robot stands still, the others keep running -------------------------
+ * Two more additive symbols: DEKF_ABI_VERSION and dekf_params are unchanged, and a caller that never calls them launches exactly the
+ * kernels of before and gets the same bits.  Without them every instance of a handle ticks, assembles and solves at every step: an
+ * environment of a vectorised simulator that is done and waits for the others, or a sweep candidate already ruled out, pays its full
+ * solve, and a robot whose link is down keeps estimating from stale latches.
+ * dekf_set_active(h, active, where): active[B], 1 runs, 0 is paused; a host or a device pointer (a device array is copied to the host
+ * and waited for, as dekf_reset_instances does).  The call states the whole mask; it is not a toggle.
+ *  - Where: direct handles only.  DEKF_ERR_INVALID for a null handle or array, for ADMM and KF handles, for solve_pipeline = 1 and for
+ *    an entry other than 0 or 1.  DEKF_ERR_ORDER before dekf_initialize.
+ *  - When: anywhere between dekf_update(h, T0 - 1) and dekf_update(h, T0).  On a two-rate handle the call may come before, between or
+ *    behind the EKF ticks of that gap.  The handle's stream waits for what dekf_reset_instances waits for.
+ *  - A paused instance stands still.  Every dekf_ekf_step and dekf_update behind the call skips it: no EKF tick, no term
+ *    construction, no arrival cost ahead of time, no solve.  Every getter keeps, to the bit, the values it had at the call: dekf_get,
+ *    dekf_get_ekf_cov, dekf_get_mhe_cov, dekf_get_solver_info, its entries of dekf_get_window and dekf_get_window_cross, and its
+ *    local step in dekf_get_instance_ticks, which is frozen.  dekf_allgather_vb contributes its frozen v_b.  VO samples pushed for it
+ *    (dekf_push_vo with its mask entry 1) are dropped, the orientation pose included.  Its IMU, leg and quaternion latches are
+ *    unspecified while it is paused (so is the quaternion of dekf_get on a handle that is fed dekf_push_quaternion).
+ *  - Resuming: its next dekf_ekf_step and dekf_update are the local tick and step that would have followed the last ones it ran.
+ *    IMU and leg samples are pushed at least once between the resuming call and its next tick or update (the rule of
+ *    dekf_reset_instances).  From then on every output of the instance (every getter above, the first K_b window and cross
+ *    entries) is bit-identical to the same instance of a handle that was never paused and received, in order, exactly the pushes,
+ *    EKF ticks and updates that occurred while the instance was active: the log with the paused steps cut out.
+ *  - Instances whose mask entry does not change keep every bit of every output at every later step.  An unchanged mask changes
+ *    nothing.
+ *  - With restarts: dekf_reset_instances on a paused instance restarts it and makes it active; its new life starts at that call.  A
+ *    restarted instance may be paused in the same gap, at local tick -1: its dekf_initialize is then the first update after it
+ *    resumes.
+ *  - With parameter tables: the rule of dekf_set_instance_params is unchanged and is read on the instance's local tick and local EKF
+ *    count, not on the handle's: a restarted instance that is paused before its first tick still takes a set while it is paused.
+ *  - dekf_reset makes every instance active: a reset handle is a fresh handle.  Pausing is state, not a setting.
+ *  - *steps of dekf_get_window and dekf_get_window_cross is the largest K_b of the batch; paused instances count with the K_b they
+ *    stand at.
+ *  - Until the first call that pauses an instance the handle launches exactly the kernels it launched before this interface
+ *    existed (a mask of ones on such a handle changes nothing).  After it, and until dekf_reset, dekf_solve_kernel_name names the
+ *    _ep twins, or the _pp twins on a handle with a parameter table, as after a restart: for a paused instance they end after the
+ *    load of its epoch.  Such a handle runs 2^31 - 2^16 steps (124 days at 200 Hz); dekf_update then returns DEKF_ERR_ORDER.
+ * dekf_get_active(h, active, where): active[B] as the last dekf_set_active and dekf_reset_instances left it; all ones where the
+ * interface was never used.  Any initialised handle; DEKF_ERR_ORDER before dekf_initialize, DEKF_ERR_INVALID for a null handle or
+ * pointer.
+ * Not part of this interface: ADMM, KF and pipelined handles; a robot that was really away (its clock did not stand still: restart
+ * it with dekf_reset_instances, do not resume it). */
+dekf_status dekf_set_active(dekf_handle h, const int* active, dekf_mem where);
+dekf_status dekf_get_active(dekf_handle h, int* active, dekf_mem where);
 
 /* status[B] values written by dekf_update */
 #define DEKF_SOLVE_NONE 0       /* no solve yet (T = 0) */

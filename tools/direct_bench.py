@@ -22,7 +22,13 @@ back, and the two alternate --repeat times in one process.  One JSON line per sh
 --instance-params measures what a parameter table (dekf_set_instance_params) costs: per mode ONE handle runs the unchanged direct
 kernels (`before`: no table), then, after dekf_reset, the _pp twins with B distinct sets (`after`), and the two alternate --repeat
 times in one process.  One JSON line per shape (--out: profiles/r12_instance_params_bench.jsonl).
-    python tools/direct_bench.py go1 --instance-params --modes direct,direct_smooth,direct_cross --repeat 3"""
+    python tools/direct_bench.py go1 --instance-params --modes direct,direct_smooth,direct_cross --repeat 3
+--epoch --paused F[,F...] measures what dekf_set_active costs and saves: per mode ONE handle restarts instance 0 and runs the epoch
+twins with every instance active (`ep`, the yardstick), then for every fraction F pauses that share of the batch, spread evenly over
+it (0: one instance paused and resumed in the same gap, so the handle launches the *_act kernels with nobody paused), and runs again
+(`paused_F`); dekf_reset brings the handle back, and the runs alternate --repeat times in one process.  One JSON line per shape
+(--out: profiles/r13_pause_bench.jsonl).
+    python tools/direct_bench.py go1 --epoch --paused 0,0.5,0.9 --modes direct,direct_smooth,direct_cross --steps 80 --repeat 3"""
 import argparse
 import json
 import os
@@ -148,6 +154,62 @@ def epoch_runs(p, B, sd, steps, mode, repeat):
             "steps_per_s_after_over_before": a["steps_per_s"] / b["steps_per_s"]}
 
 
+def pause_ticks(p, steps, fractions):
+    """(W, refill, log length) of pause_runs"""
+    W, refill = max(p.N + 10, 64), p.N + 10
+    return W, refill, W + refill + 2 * steps * (1 + len(fractions))
+
+
+def pause_runs(p, B, sd, steps, mode, repeat, fractions):
+    """the epoch twins with every instance active, then with the fractions of the batch paused, on one handle, `repeat` times in turn"""
+    import numpy as np
+    W, refill, _ = pause_ticks(p, steps, fractions)
+    est = BatchedEstimator(p, B, **MODES[mode])
+    first = np.zeros(B, np.int32)
+    first[0] = 1
+    runs = {"ep": [], **{f"paused_{f:g}": [] for f in fractions}}
+    for _ in range(repeat):
+        est.reset()
+        for k in range(W):
+            est.push_stream_step(sd, k)
+            est.step(k)
+        est.reset_instances(first)
+        for k in range(W, W + refill):
+            est.push_stream_step(sd, k)
+            est.step(k)
+        k0 = W + refill
+        runs["ep"].append(timed(est, sd, k0, steps, B))
+        assert runs["ep"][-1]["kernel"].endswith("_ep") and int(est.active().sum()) == B
+        for f in fractions:
+            k0 += 2 * steps
+            b = np.arange(B)
+            active = 1 - (np.floor((b + 1) * f) > np.floor(b * f)).astype(np.int32)
+            if active.all():  # nobody paused: the *_act kernels all the same
+                one_paused = np.ones(B, np.int32)
+                one_paused[B // 2] = 0
+                est.set_active(one_paused)
+            est.set_active(active)
+            r = timed(est, sd, k0, steps, B)
+            r["paused"] = int(B - est.active().sum())
+            runs[f"paused_{f:g}"].append(r)
+            est.set_active(np.ones(B, np.int32))
+        assert float((est.get()["status"] == 1).mean()) == 1.0
+
+    def best(rs):
+        out = dict(max(rs, key=lambda r: r["steps_per_s"]))
+        for c in ("solve", "assemble", "ekf"):
+            out[f"{c}_ms"] = min(r[f"{c}_ms"] for r in rs)
+        out["all_steps_per_s"] = [r["steps_per_s"] for r in rs]
+        out["all_solve_ms"] = [r["solve_ms"] for r in rs]
+        return out
+    est.close()
+    out = {k: best(v) for k, v in runs.items()}
+    for k in list(out):
+        if k != "ep":
+            out[k].update({f"{c}_over_ep": out[k][c] / out["ep"][c] for c in ("solve_ms", "assemble_ms", "ekf_ms", "steps_per_s")})
+    return out
+
+
 def distinct_sets(p, B):
     """B parameter sets, no two alike: every std of the noise fields scaled by a factor of its own in [0.8, 1.25]"""
     fields = ("p_init_std", "v_init_std", "foot_init_std", "accel_bias_init_std", "p_process_std", "accel_input_std", "gyro_input_std",
@@ -205,8 +267,14 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--epoch", action="store_true", help="the same handle before and after a first dekf_reset_instances")
     ap.add_argument("--instance-params", action="store_true", help="the same handle without and with a table of B distinct parameter sets")
+    ap.add_argument("--paused", default=None, help="with --epoch: fractions of the batch to pause (dekf_set_active), e.g. 0,0.5,0.9")
     a = ap.parse_args()
     modes = a.modes.split(",")
+    fractions = [float(f) for f in a.paused.split(",")] if a.paused else []
+    if fractions and not a.epoch:
+        ap.error("--paused goes with --epoch")
+    if a.out is None and fractions:
+        a.out = os.path.join(ROOT, "profiles", "r13_pause_bench.jsonl")
     if a.out is None and a.instance_params:
         a.out = os.path.join(ROOT, "profiles", "r12_instance_params_bench.jsonl")
     if a.out is None and a.epoch:
@@ -224,6 +292,16 @@ def main():
             sd = streams_to_device(make_streams(p, B, max(p.N + 10, 64) + 2 * a.steps))
             line = {"shape": name, "batch": B, "N": int(p.N), "steps": a.steps, "repeat": a.repeat, "instance_params": True}
             line.update({mode: instance_params_runs(p, B, sd, a.steps, mode, a.repeat) for mode in modes})
+            print(json.dumps(line), flush=True)
+            with open(a.out, "a") as f:
+                f.write(json.dumps(line) + "\n")
+            del sd
+            torch.cuda.empty_cache()
+            continue
+        if a.epoch and fractions:
+            sd = streams_to_device(make_streams(p, B, pause_ticks(p, a.steps, fractions)[2]))
+            line = {"shape": name, "batch": B, "N": int(p.N), "steps": a.steps, "repeat": a.repeat, "paused": fractions}
+            line.update({mode: pause_runs(p, B, sd, a.steps, mode, a.repeat, fractions) for mode in modes})
             print(json.dumps(line), flush=True)
             with open(a.out, "a") as f:
                 f.write(json.dumps(line) + "\n")
