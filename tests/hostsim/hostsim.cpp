@@ -88,6 +88,9 @@ void hs_update(void* hv, int T) {
     Sim* h = (Sim*)hv;
     for (int b = 0; b < h->c.B; ++b) {
         if (h->c.est_type == 0) {
+#ifdef HS_KF_ONLY  // a stand-alone driver that steps est_type 1 only spares itself the instantiation of every solve kernel
+            std::abort();
+#else
             assemble_update(h->c, h->s, b, T, h->pushes, h->lds.data());
             int kstart = T - h->c.N + 1 > 0 ? T - h->c.N + 1 : 0;
             SolveLayout lay; lay.init(h->c.N, h->c.L, h->c.ft);
@@ -115,6 +118,7 @@ void hs_update(void* hv, int T) {
             }
 #undef HS_SOLVE
 #undef HS_SOLVE_FOOT
+#endif
         } else {
             kf_update(h->c, h->s, b, h->pushes, h->lds.data());
         }
@@ -143,6 +147,11 @@ void hs_get_residuals(void* hv, double* pri, double* dua) {
 void hs_get_ekf_cov(void* hv, double* P) {
     Sim* h = (Sim*)hv; size_t B = h->c.B;
     for (size_t b = 0; b < B; ++b) for (int i = 0; i < 16; ++i) P[16 * b + i] = h->s.ekf_P[(size_t)i * B + b];
+}
+// est_type 1: the filter's covariance after the last tick, [B][ns][ns] (what dekf_get_kf_cov hands out)
+void hs_get_kf_cov(void* hv, double* Cm) {
+    Sim* h = (Sim*)hv;
+    std::memcpy(Cm, h->s.kf_C, (size_t)h->c.ns * h->c.ns * h->c.B * 8);
 }
 void hs_get_arrival(void* hv, double* M, double* n) {
     Sim* h = (Sim*)hv; size_t B = h->c.B;

@@ -77,6 +77,7 @@ def _bind(L):
     L.hs_update.argtypes = [vp, C.c_int]
     L.hs_get.argtypes = [vp, _dp, _dp, _dp, _dp, _ip, _ip, _ip]
     L.hs_get_ekf_cov.argtypes = [vp, _dp]
+    L.hs_get_kf_cov.argtypes = [vp, _dp]
     L.hs_get_polish_status.argtypes = [vp, _ip]
     L.hs_get_residuals.argtypes = [vp, _dp, _dp]
     L.hs_get_arrival.argtypes = [vp, _dp, _dp]
@@ -126,6 +127,13 @@ class HostSim:
         P = np.zeros((self.B, 4, 4))
         self.L.hs_get_ekf_cov(self.h, _p(P))
         return P
+
+    def kf_cov(self):
+        """est_type 1: the filter's covariance after the last tick, [B, ns, ns]"""
+        ns = self.p.dim_state
+        Cm = np.zeros((self.B, ns, ns))
+        self.L.hs_get_kf_cov(self.h, _p(Cm))
+        return Cm
 
     def arrival(self):
         ns = self.p.dim_state
