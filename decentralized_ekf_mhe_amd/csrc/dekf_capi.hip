@@ -14,6 +14,7 @@
 #include "mhe_assemble_core.h"
 #include "mhe_direct_core.h"
 #include "mhe_epoch_core.h"
+#include "mhe_innov_core.h"
 #include "mhe_params_core.h"
 #include "mhe_pause_core.h"
 #include "mhe_solve_core.h"
@@ -44,6 +45,16 @@ __global__ void k_mhe_marginalize_early(DevCfg c, DevState s, int T);
     __global__ void NAME##_smooth_pp(DevState s, int T, double* cov, DirectWindow win, const int* t0, const DevCfg* pc); \
     __global__ void NAME##_smooth_cross_pp(DevState s, int T, double* cov, DirectWindow win, DirectCross cross, const int* t0, const DevCfg* pc);
 #include "direct_kernels.def"
+// the innovation kernels behind the direct solve (mhe_innov_core.h), one per leg count, and their epoch twins
+#define DEKF_INNOV_KERNEL(L)                                                                                          \
+    __global__ void k_mhe_innov_##L(DevCfg c, DevState s, int kstart, int K, const double* cov, InnovStore out);      \
+    __global__ void k_mhe_innov_##L##_ep(DevCfg c, DevState s, int T, const double* cov, InnovStore out, const int* t0);
+DEKF_INNOV_KERNEL(1)
+DEKF_INNOV_KERNEL(2)
+DEKF_INNOV_KERNEL(3)
+DEKF_INNOV_KERNEL(4)
+#undef DEKF_INNOV_KERNEL
+__global__ void k_innov_nan(DevCfg c, const int* mask, InnovStore out);
 __global__ void k_gap();
 __global__ void k_kf_initialize(DevCfg c, DevState s);
 __global__ void k_kf_update(DevCfg c, DevState s, int pushes);
@@ -123,6 +134,12 @@ struct dekf_handle_s {
     // win.t1's entries into Cov(x_k, x_{k+1}) and leaves Cov(x_k, x_T) in cross_st.newest (mhe_direct_core.h: DirectCross)
     bool cross = false;
     DirectCross cross_st;
+    // dekf_set_innovation: an innovation handle launches the innovation kernel of its leg count (mhe_innov_core.h) behind the direct
+    // kernel, whichever twin that is, on the same stream; it leaves the five arrays of dekf_get_innovation in innov_st (one block).
+    // innov_valid: an update has written them since dekf_create / dekf_reset
+    bool innov = false;
+    InnovStore innov_st;
+    bool innov_valid = false;
     // dekf_reset_instances: the epochs of a direct handle (mhe_epoch_core.h).  ep_t0 | ep_c0: [B] ints each on the device, the handle's
     // step and EKF tick count at every instance's last restart (0: never), allocated by the first call with a non-zero mask; t0_host:
     // the host's copy of ep_t0 (dekf_get_instance_ticks, the window getters' steps), min_t0 its smallest entry; c0_host: the host's copy
@@ -293,6 +310,13 @@ const DirectKernel* direct_kernel(int L, int ft, int N) {
     return any;
 }
 
+// The innovation kernels as dekf_set_innovation selects them: by leg count, the kernel and its epoch twin
+typedef void (*InnovFn)(DevCfg, DevState, int, int, const double*, InnovStore);
+typedef void (*InnovEpochFn)(DevCfg, DevState, int, const double*, InnovStore, const int*);
+struct InnovKernel { InnovFn fn; InnovEpochFn fn_ep; };
+const InnovKernel innov_kernels[DEKF_MAX_LEGS] = {{k_mhe_innov_1, k_mhe_innov_1_ep}, {k_mhe_innov_2, k_mhe_innov_2_ep},
+                                                  {k_mhe_innov_3, k_mhe_innov_3_ep}, {k_mhe_innov_4, k_mhe_innov_4_ep}};
+
 // the kernel of its row that a direct handle launches: the smoother and cross settings pick the twin, and a handle that has restarted
 // an instance (epochs) launches the epoch twin of that one, which finds every instance's window from the step; a handle with a
 // parameter table (pp) the parameter twin of the epoch twin, with or without a restarted instance
@@ -308,14 +332,20 @@ struct SolveLaunch {
     int grid, threads; size_t lds;
     SolveFn admm;           // the ADMM kernel; null on a direct handle, which launches ...
     DirectVariant variant;  // ... this kernel of its row (h->direct)
+    // ... and behind it, on an innovation handle (dekf_set_innovation), the innovation kernel of its leg count (null: none): the epoch
+    // twin where the direct kernel is an epoch or parameter twin.  One wavefront per instance, a grid of B, lds_innov of LDS
+    const InnovKernel* innov;
+    size_t lds_innov;
 };
 SolveLaunch solve_launch(const dekf_handle_s* h, int K) {
     const DirectVariant v = direct_variant(h);
-    if (h->solver == DEKF_SOLVER_DIRECT) return {h->direct->name[v], h->c.B, 64, h->lds_direct, nullptr, v};
+    if (h->solver == DEKF_SOLVER_DIRECT)
+        return {h->direct->name[v], h->c.B, 64, h->lds_direct, nullptr, v, h->innov ? &innov_kernels[h->c.L - 1] : nullptr,
+                (size_t)InnovScratch::len(h->c.L) * sizeof(double)};
     const bool full = h->solve_entry_full && K == h->c.N;
     const SolveTwin t = solve_twin(full ? h->solve_entry_full : h->solve_entry, h->c.polish != 0, h->c.warm != 0);
-    if (full) return {t.name, h->solve_grid_full, h->solve_threads_full, h->lds_solve_full, t.fn, v};
-    return {t.name, h->solve_grid, DEKF_SOLVE_THREADS, h->lds_solve, t.fn, v};
+    if (full) return {t.name, h->solve_grid_full, h->solve_threads_full, h->lds_solve_full, t.fn, v, nullptr, 0};
+    return {t.name, h->solve_grid, DEKF_SOLVE_THREADS, h->lds_solve, t.fn, v, nullptr, 0};
 }
 
 // A family of full-window kernels (K == N): the shapes it covers are the rows of its role in solve_kernels.def
@@ -557,6 +587,10 @@ void launch_solve(dekf_handle h, const SolveLaunch& l, const DevState& sp, int T
     case smooth_pp: d.fn_smooth_pp<<<l.grid, l.threads, l.lds, ss>>>(sp, T, h->mhe_cov, h->win, h->ep_t0, h->pp_mhe); break;
     case cross_pp: d.fn_cross_pp<<<l.grid, l.threads, l.lds, ss>>>(sp, T, h->mhe_cov, h->win, h->cross_st, h->ep_t0, h->pp_mhe); break;
     }
+    if (!l.innov) return;
+    // (an innovation handle: the statistics of the newest step from what the solve just left, in stream order behind it)
+    if (l.variant >= plain_ep) l.innov->fn_ep<<<l.grid, 64, l.lds_innov, ss>>>(h->c, sp, T, h->mhe_cov, h->innov_st, h->ep_t0);
+    else l.innov->fn<<<l.grid, 64, l.lds_innov, ss>>>(h->c, sp, kstart, K, h->mhe_cov, h->innov_st);
 }
 
 // the solve of step T behind its terms, and what the getters need to know about it
@@ -582,7 +616,7 @@ dekf_status solve_step(dekf_handle h, const MheStep& st) {
         { static const int gap = getenv("DEKF_DEBUG_GAP_KERNEL") ? atoi(getenv("DEKF_DEBUG_GAP_KERNEL")) : 0;
           for (int i = 0; i < gap; ++i) k_gap<<<1, 64, 0, ss>>>(); }
 #endif
-        launch_solve(h, solve_launch(h, K), st.sp, T, kstart, K, ss);
+        launch_solve(h, solve_launch(h, K), st.sp, T, kstart, K, ss);  // (with the innovation kernel of an innovation handle: one launch of class 2)
     }
     if (h->pipelined) {
         HIPCHK(hipEventRecord(h->ev_solve[par], ss));
@@ -592,6 +626,7 @@ dekf_status solve_step(dekf_handle h, const MheStep& st) {
     }
     h->last_par = par;
     h->mhe_cov_valid = h->solver == DEKF_SOLVER_DIRECT;
+    h->innov_valid = h->innov;
     h->win_steps = h->smoother ? K : 0;
     if (h->epochs && h->smoother) {  // the largest window of the batch: the instance restarted longest ago (none at its local step 0),
         const int Ta = T - h->min_t0;  // or a paused one with the window it stands at
@@ -822,7 +857,10 @@ dekf_status dekf_reset(dekf_handle h) {
     }
     h->last_par = h->ekf_count = h->pushes = h->next_T = 0;
     h->initialized = false;
-    h->mhe_cov_valid = false;  // (the solver, smoother and cross settings survive)
+    h->mhe_cov_valid = false;  // (the solver, smoother, cross and innovation settings survive)
+    h->innov_valid = false;
+    if (h->innov_st.nu)  // every entry NaN again (all bits set is one): an instance keeps it until its first solve
+        HIPCHK(hipMemsetAsync(h->innov_st.nu, 0xff, (size_t)h->c.B * InnovStore::len(h->c.L) * sizeof(double), h->stream));
     h->win_steps = 0;
     if (h->ep_t0) {  // every epoch: the handle launches the kernels of a handle that never restarted an instance again
         HIPCHK(hipMemsetAsync(h->ep_t0, 0, 2 * (size_t)h->c.B * sizeof(int), h->stream));
@@ -869,6 +907,7 @@ dekf_status dekf_reset_instances(dekf_handle h, const int* mask, dekf_mem where)
     if (h->pp)  // (every instance's own initial EKF state)
         k_reset_instances_pp<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->s, dmask, h->mhe_cov, h->ep_t0, h->ep_c0, h->next_T, h->ekf_count, h->pp_ekf);
     else k_reset_instances<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->s, dmask, h->mhe_cov, h->ep_t0, h->ep_c0, h->next_T, h->ekf_count);
+    if (h->innov_st.nu) k_innov_nan<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, dmask, h->innov_st);  // (NaN until its first solve, as cov)
     HIPCHK(hipGetLastError());
     if (where == DEKF_HOST) HIPCHK(hipStreamSynchronize(h->stream));  // (m, a local, is the source of the copy)
     for (size_t b = 0; b < B; ++b)  // (a paused instance that is restarted is active: its new life starts here)
@@ -1298,7 +1337,8 @@ dekf_status dekf_set_solver(dekf_handle h, int solver) {
     }
     h->solver = solver;
     h->mhe_cov_valid = false;
-    if (solver == DEKF_SOLVER_ADMM) h->smoother = h->cross = false;  // the smoother and its cross-covariances are the direct solve's
+    if (solver == DEKF_SOLVER_ADMM) h->smoother = h->cross = h->innov = false;  // the smoother, its cross-covariances and the innovation statistics are the direct solve's
+    h->innov_valid = false;
     h->win_steps = 0;
     return DEKF_OK;
 }
@@ -1358,6 +1398,42 @@ dekf_status dekf_get_window_cross(dekf_handle h, int* steps, double* cov_lag1, d
     TRY(fetch_rows(h, cov_lag1, h->win.t1, (N - 1) * n2 * 8, (K - 1) * n2 * 8, B, where));
     TRY(fetch_rows(h, cov_newest, h->cross_st.newest, N * n2 * 8, K * n2 * 8, B, where));
     return cov_lag1 || cov_newest ? host_sync(h, where) : DEKF_OK;
+}
+
+dekf_status dekf_set_innovation(dekf_handle h, int on) {
+    if (!h) return fail(DEKF_ERR_INVALID, "null handle");
+    if (on != 0 && on != 1) return fail(DEKF_ERR_INVALID, "dekf_set_innovation: on must be 0 or 1");
+    if (on && h->solver != DEKF_SOLVER_DIRECT) return fail(DEKF_ERR_INVALID, "the innovation statistics need a direct handle (dekf_set_solver(h, DEKF_SOLVER_DIRECT))");
+    if (on && h->c.ft) return fail(DEKF_ERR_INVALID, "the innovation statistics are not available with foot-position states (leg_odom_type 1)");
+    if (h->initialized) return fail(DEKF_ERR_ORDER, "dekf_set_innovation is allowed before dekf_initialize or right after dekf_reset");
+    if (on && !h->innov_st.nu) {
+        HIPCHK(hipSetDevice(h->device));
+        const size_t B = (size_t)h->c.B, L = (size_t)h->c.L, nm = 3 * L;
+        double* q = nullptr;
+        TRY(dev_alloc(h, B * InnovStore::len(h->c.L) * sizeof(double), &q));  // nu | S | nis | nis_leg | loglik in one block
+        HIPCHK(hipMemsetAsync(q, 0xff, B * InnovStore::len(h->c.L) * sizeof(double), h->stream));  // (NaN: an instance keeps it until its first solve)
+        h->innov_st.nu = q;
+        h->innov_st.S = q + B * nm;
+        h->innov_st.nis = h->innov_st.S + B * nm * nm;
+        h->innov_st.nis_leg = h->innov_st.nis + B;
+        h->innov_st.loglik = h->innov_st.nis_leg + B * L;
+    }
+    h->innov = on != 0;
+    h->innov_valid = false;
+    return DEKF_OK;
+}
+
+dekf_status dekf_get_innovation(dekf_handle h, double* innov, double* innov_cov, double* nis, double* nis_leg, double* loglik, dekf_mem where) {
+    if (!h) return fail(DEKF_ERR_INVALID, "null handle");
+    if (!h->innov) return fail(DEKF_ERR_INVALID, "dekf_get_innovation needs an innovation handle (dekf_set_innovation(h, 1))");
+    if (!h->innov_valid) return fail(DEKF_ERR_ORDER, "dekf_get_innovation before the first update (since dekf_create or dekf_reset)");
+    const size_t B = (size_t)h->c.B, L = (size_t)h->c.L, nm = 3 * L;
+    TRY(fetch(h, innov, h->innov_st.nu, B * nm * 8, where));
+    TRY(fetch(h, innov_cov, h->innov_st.S, B * nm * nm * 8, where));
+    TRY(fetch(h, nis, h->innov_st.nis, B * 8, where));
+    TRY(fetch(h, nis_leg, h->innov_st.nis_leg, B * L * 8, where));
+    TRY(fetch(h, loglik, h->innov_st.loglik, B * 8, where));
+    return innov || innov_cov || nis || nis_leg || loglik ? host_sync(h, where) : DEKF_OK;
 }
 
 dekf_status dekf_get_mhe_cov(dekf_handle h, double* cov, dekf_mem where) {

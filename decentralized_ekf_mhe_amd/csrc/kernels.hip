@@ -7,6 +7,7 @@
 //                     from one XCD (its L2 is the only one that caches it)
 //                     (mhe_solve_core.h, mhe_admm_core.h)
 //   k_mhe_solve_direct_*  the direct solve (dekf_set_solver), one wavefront per instance (mhe_direct_core.h)
+//   k_mhe_innov_*     the innovation statistics behind the direct solve (dekf_set_innovation), one wavefront per instance (mhe_innov_core.h)
 //   k_kf_*            KF alternative                      (kf_core.h)
 //   k_latch_vo        masked VO latch (robotSub::vo_callback for a batch)
 //   k_latch4          device-to-device sensor latch of one push (IMU or leg arrays) in one launch
@@ -22,6 +23,7 @@
 #include "mhe_assemble_core.h"
 #include "mhe_direct_core.h"
 #include "mhe_epoch_core.h"
+#include "mhe_innov_core.h"
 #include "mhe_params_core.h"
 #include "mhe_pause_core.h"
 #include "mhe_solve_core.h"
@@ -120,6 +122,13 @@ extern "C" {
 #define DEKF_MISC_KERNELS 1
 #else
 #define DEKF_MISC_KERNELS 0
+#endif
+// ... and the innovation kernels (dekf_set_innovation) only with bit 2048: a unit of their own in the product build, whose resource
+// remarks go to a file of their own (build.sh), so that the compiler's account of the kernels of before stays the file it was
+#if !defined(DEKF_KSET_ONLY) || (defined(DEKF_KSET) && (DEKF_KSET & 2048))
+#define DEKF_INNOV_KERNELS 1
+#else
+#define DEKF_INNOV_KERNELS 0
 #endif
 #if DEKF_MISC_KERNELS
 __global__ void __launch_bounds__(64) k_ekf_tick(DevCfg c, DevState s, int count) {
@@ -342,6 +351,46 @@ __global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_assemble_act_pp(DevS
     __global__ void NAME##_smooth_cross_pp(DevState, int, double*, DirectWindow, DirectCross, const int*, const DevCfg*) {}
 #endif
 #include "direct_kernels.def"
+
+#if DEKF_INNOV_KERNELS
+// The innovation kernels (dekf_set_innovation, mhe_innov_core.h): launched behind the direct solve on its stream, one wavefront per
+// instance, a grid of B; one per leg count (foot-state handles are outside the interface).  They read what the solve left (x_mhe, the
+// status, cov) and the newest window record.  Kernels of their own, in a set of their own (bit 2048, below): the direct kernels are the
+// code they were, and every build without -DDEKF_KSET_ONLY carries these, whatever its mask.
+// The epoch twin k_mhe_innov_L_ep is what a handle launches that launches the direct kernels' epoch or parameter twins: it takes the
+// handle's step T in place of (kstart, K) and finds its instance's newest record from the local step, or does nothing below a local
+// step of 1 (a restarted instance at its step 0, a paused instance).  No parameter twin: the record carries the instance's own Q_m,
+// and all the kernel reads of DevCfg is the structure, which is the handle's.
+#define DEKF_INNOV_KERNEL(L)                                                                                                  \
+    __global__ void __launch_bounds__(64) k_mhe_innov_##L(DevCfg c, DevState s, int kstart, int K, const double* cov, InnovStore out) { \
+        extern __shared__ double lds[];                                                                                      \
+        innovation_t<L>(c, s, blockIdx.x, (kstart + K - 1) % c.wcap, cov, out, lds);                                          \
+    }                                                                                                                        \
+    __global__ void __launch_bounds__(64) k_mhe_innov_##L##_ep(DevCfg c, DevState s, int T, const double* cov, InnovStore out, \
+                                                               const int* t0) {                                              \
+        extern __shared__ double lds[];                                                                                      \
+        int kstart, K;                                                                                                       \
+        if (direct_window_epoch(c, T, t0[blockIdx.x], kstart, K))                                                            \
+            innovation_t<L>(c, s, blockIdx.x, (kstart + K - 1) % c.wcap, cov, out, lds);                                      \
+    }
+DEKF_INNOV_KERNEL(1)
+DEKF_INNOV_KERNEL(2)
+DEKF_INNOV_KERNEL(3)
+DEKF_INNOV_KERNEL(4)
+#undef DEKF_INNOV_KERNEL
+// dekf_reset_instances of an innovation handle (dekf_set_innovation), behind the kernel above: the restarted instances' entries of the
+// five arrays NaN until their first solve, as their block of cov.  A kernel of its own: k_reset_instances stays the code it was
+__global__ void k_innov_nan(DevCfg c, const int* mask, InnovStore out) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= c.B || !mask[b]) return;
+    const int nm = c.nm, L = c.L;
+    for (int i = 0; i < nm; ++i) out.nu[(size_t)nm * b + i] = NAN;
+    for (int i = 0; i < nm * nm; ++i) out.S[(size_t)nm * nm * b + i] = NAN;
+    for (int i = 0; i < L; ++i) out.nis_leg[(size_t)L * b + i] = NAN;
+    out.nis[b] = NAN;
+    out.loglik[b] = NAN;
+}
+#endif  // DEKF_INNOV_KERNELS
 
 #if DEKF_MISC_KERNELS
 __global__ void k_gap() {}

@@ -57,13 +57,15 @@ def relative_cov(cov_win, cov_newest, k):
 
 class BatchedEstimator:
     def __init__(self, params: DekfParams, batch: int, device: int = 0, stream=None, warm_start: bool = False, solver: str = "admm",
-                 smoother: bool = False, cross: bool = False):
+                 smoother: bool = False, cross: bool = False, innovation: bool = False):
         """warm_start: full-window solves start from the previous tick's shifted solution (dekf_set_warm_start; off by default).
         solver: "admm" (default, the reference's OSQP-style ADMM) or "direct" (the exact optimum of the window QP and its covariance,
         dekf_set_solver; see mhe_cov)
         smoother: a direct handle also leaves every state of the window and its covariance (dekf_set_smoother; see window)
         cross: a smoothing handle also leaves the window's lag-one and to-newest cross-covariances (dekf_set_window_cross; see
-        window_cross).  It implies nothing else: without smoother=True the library refuses it"""
+        window_cross).  It implies nothing else: without smoother=True the library refuses it
+        innovation: a direct handle also leaves the innovation of the newest leg measurement, its covariance, the NIS (whole and per
+        leg) and the predictive log-likelihood of every tick (dekf_set_innovation; see innovation)"""
         if solver not in ("admm", "direct"):
             raise ValueError(f"solver must be 'admm' or 'direct', not {solver!r}")
         _torch_runtime_first()
@@ -82,6 +84,8 @@ class BatchedEstimator:
                 capi.check(self.lib.dekf_set_smoother(self.h, 1))
             if cross:
                 capi.check(self.lib.dekf_set_window_cross(self.h, 1))
+            if innovation:
+                capi.check(self.lib.dekf_set_innovation(self.h, 1))
             if warm_start:
                 capi.check(self.lib.dekf_set_warm_start(self.h, 1))
         except capi.DekfError:
@@ -269,6 +273,17 @@ class BatchedEstimator:
         K = C.c_int(0)
         capi.check(self.lib.dekf_get_window_cross(self.h, C.byref(K), C.c_void_p(l1.ctypes.data), C.c_void_p(zn.ctypes.data), capi.DEKF_HOST))
         return K.value, l1[:, :K.value - 1].copy(), zn[:, :K.value].copy()
+
+    def innovation(self):
+        """the innovation statistics of the last update of an innovation handle (dekf_get_innovation), a dict: innov [B, nm] = y - H x^-,
+        innov_cov [B, nm, nm] = S, nis [B], nis_leg [B, L] and loglik [B] = log p(y_T | the rest of the window), nm = 3 num_legs.  NaN for
+        an instance whose solve failed or that has not solved since its restart.  Summed over a log, loglik is the score of the
+        instance's noise set; nis_leg is chi-square with 3 degrees of freedom on a consistent estimator"""
+        B, L = self.batch, self.params.num_legs
+        out = dict(innov=np.zeros((B, 3 * L)), innov_cov=np.zeros((B, 3 * L, 3 * L)), nis=np.zeros(B), nis_leg=np.zeros((B, L)), loglik=np.zeros(B))
+        capi.check(self.lib.dekf_get_innovation(self.h, *[C.c_void_p(out[k].ctypes.data) for k in ("innov", "innov_cov", "nis", "nis_leg", "loglik")],
+                                                capi.DEKF_HOST))
+        return out
 
     def kf_cov(self):
         ns = self.params.dim_state

@@ -461,6 +461,51 @@ dekf_status dekf_get_instance_params(dekf_handle h, int b, dekf_params* out);
 dekf_status dekf_set_active(dekf_handle h, const int* active, dekf_mem where);
 dekf_status dekf_get_active(dekf_handle h, int* active, dekf_mem where);
 
+/* ---- innovation statistics (opt-in, direct handles): do the newest measurements agree with the estimate? -----------------
+ * Two more additive symbols: DEKF_ABI_VERSION and dekf_params are unchanged, and a caller that never calls them launches exactly the
+ * kernels of before and gets the same bits.  A direct handle returns an estimate and its covariance; these return the numbers that say
+ * whether the newest leg measurement agrees with them: its innovation and innovation covariance, the normalised innovation squared
+ * (NIS), whole and per leg, and the predictive log-likelihood of the tick.  Summed over a log, loglik is the score of a noise set
+ * (with dekf_set_instance_params: B candidate sets on one log give B scores in one pass, no ground truth needed); nis_leg against its
+ * chi-square bound (3 degrees of freedom) is the usual test for a stance foot that slips.
+ * dekf_set_innovation(h, on), on = 0 (default) or 1.  Call order as for dekf_set_smoother: before dekf_initialize or right after
+ * dekf_reset (else DEKF_ERR_ORDER); the setting survives dekf_reset.  DEKF_ERR_INVALID for a null handle, any other `on`, on = 1 on a
+ * handle that is not a direct handle (ADMM, KF) and on = 1 on a handle with leg_odom_type = 1.  dekf_set_solver(h, DEKF_SOLVER_ADMM)
+ * switches the option off, as it does the smoother; going back to DEKF_SOLVER_DIRECT does not switch it on again.  The option is
+ * independent of dekf_set_smoother and dekf_set_window_cross: any combination is allowed.  The first enable allocates the stores:
+ * 3L + 9L^2 + 2 + L doubles per instance, L = num_legs (Go1: 162 doubles).
+ * An innovation handle's update launches one small kernel (k_mhe_innov_<L>, or its epoch twin k_mhe_innov_<L>_ep behind an epoch or
+ * parameter twin of the direct kernel) behind the direct solve on the same stream; timing class 2 brackets the two as one launch.
+ * It leaves, per instance and update that solved (window-fill and full windows alike), for the newest step T, with nm = 3 num_legs:
+ *  - x^- and P^-: the newest state and its covariance block of the minimiser of the QP the direct solve minimises WITH THE NEWEST
+ *    STEP'S MEAS ROWS MADE FREE, i.e. everything the window knows about x_T except this tick's leg measurement; H and y: those rows'
+ *    state coefficients and bound; Q_m: their slacks' cost;
+ *  - innov[b][:] = nu = y - H x^-;
+ *  - innov_cov[b][:][:] = S = H P^- H' + Q_m^-1, row-major and symmetric to the bit;
+ *  - nis[b] = nu' S^-1 nu;
+ *  - nis_leg[b][l] = nu_l' (S_ll)^-1 nu_l, from leg l's 3-block of nu and its 3 x 3 diagonal block of S;
+ *  - loglik[b] = -1/2 (nis + log det S + nm log 2 pi) = log p(y_T | the rest of the window problem).
+ * No second elimination: with P = Cov(x_T) and e = y - H x_T, S^-1 = Q_m - Q_m H P H' Q_m and nu = S Q_m e (Woodbury).
+ *  - x_mhe, v_b, status, solver info, dekf_get_mhe_cov, dekf_get_window and dekf_get_window_cross are bit-identical to the same handle
+ *    with the option off; dekf_solve_kernel_name is unchanged: the solve kernel is the same one.
+ *  - An instance whose status is DEKF_SOLVE_NUMERIC, or whose S^-1 has a pivot that is not positive and finite, gets NaN in all five
+ *    arrays.  Its status is not changed; its neighbours are unaffected.
+ *  - An instance at its local step 0 (restarted by dekf_reset_instances, at dekf_update(h, T0)) has no solve: it holds NaN from the
+ *    dekf_reset_instances call on until its first solve.  A paused instance (dekf_set_active) keeps every bit it had at the pausing call.
+ *  - On a handle with a parameter table instance b gives the bits of a handle created with its set; after a restart, of a fresh handle
+ *    fed the samples from the restart on.  A robot's five arrays do not depend on the batch it runs in, nor on the smoother or the
+ *    cross-covariances being on.
+ * dekf_get_innovation: innov[B][nm], innov_cov[B][nm][nm], nis[B], nis_leg[B][num_legs], loglik[B].  Any pointer may be NULL.  Host
+ * pointers: copy and synchronise; device pointers: in stream order, like dekf_get_mhe_cov.  DEKF_ERR_INVALID on a handle without the
+ * option, DEKF_ERR_ORDER before the first update and after dekf_reset until the next update.
+ * Not part of this interface: ADMM and KF handles; handles with foot-position states (leg_odom_type 1: a foot that touches down
+ * carries a prior variance of about 1e14 against a measurement variance of about 1e-6, and Q_m - Q_m H P H' Q_m cancels completely);
+ * the likelihood of the VO rows (they turn into equalities steps after the fact, so vo_p_std is not scored by this number); and
+ * whole-window likelihoods. */
+dekf_status dekf_set_innovation(dekf_handle h, int on);
+dekf_status dekf_get_innovation(dekf_handle h, double* innov, double* innov_cov, double* nis, double* nis_leg, double* loglik,
+                                dekf_mem where);
+
 /* status[B] values written by dekf_update */
 #define DEKF_SOLVE_NONE 0       /* no solve yet (T = 0) */
 #define DEKF_SOLVE_OK 1         /* OSQP_SOLVED */

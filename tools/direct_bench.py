@@ -15,6 +15,8 @@ alternate inside one process, so that a drift of the machine does not land on on
     python tools/direct_bench.py [shape ...] [--steps 200] [--modes cold,warm,direct] [--repeat 1] [--out FILE]
     python tools/direct_bench.py --modes direct,direct_smooth --repeat 3          # the smoother against its yardstick
     python tools/direct_bench.py --modes direct,direct_smooth,direct_cross --repeat 3   # the cross-covariances against theirs
+    python tools/direct_bench.py go1 cassie pogox --modes direct,direct_innov --repeat 3   # the innovation statistics (dekf_set_innovation;
+                                                     # profiles/r10_innovation_bench.jsonl; not for go1_foot: outside the interface)
 --epoch measures what dekf_reset_instances costs the instances it does not restart: per mode ONE handle runs the unchanged direct
 kernel (`before`), then restarts instance 0, lets its window refill and runs the epoch twins (`after`); dekf_reset brings the handle
 back, and the two alternate --repeat times in one process.  One JSON line per shape (--out: profiles/r11_epoch_bench.jsonl).
@@ -51,7 +53,8 @@ SHAPES = {
     "go1_foot": (go1_params, 4096, {"leg_odom_type": 1}),
 }
 MODES = {"cold": dict(), "warm": dict(warm_start=True), "direct": dict(solver="direct"),
-         "direct_smooth": dict(solver="direct", smoother=True), "direct_cross": dict(solver="direct", smoother=True, cross=True)}
+         "direct_smooth": dict(solver="direct", smoother=True), "direct_cross": dict(solver="direct", smoother=True, cross=True),
+         "direct_innov": dict(solver="direct", innovation=True)}
 
 
 def one(p, B, sd, W, steps, mode):
@@ -280,7 +283,8 @@ def main():
     if a.out is None and a.epoch:
         a.out = os.path.join(ROOT, "profiles", "r11_epoch_bench.jsonl")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "r10_cross_bench.jsonl" if "direct_cross" in modes else
+        a.out = os.path.join(ROOT, "profiles", "r10_innovation_bench.jsonl" if "direct_innov" in modes else
+                             "r10_cross_bench.jsonl" if "direct_cross" in modes else
                              "r09_smoother_bench.jsonl" if "direct_smooth" in modes else "r08_direct_bench.jsonl")
     for name in a.shapes:
         maker, B, kw = SHAPES[name]
@@ -337,6 +341,9 @@ def main():
         if "direct" in line and "direct_smooth" in line:
             line["smooth_solve_ms_over_direct"] = line["direct_smooth"]["solve_ms"] / line["direct"]["solve_ms"]
             line["smooth_steps_per_s_over_direct"] = line["direct_smooth"]["steps_per_s"] / line["direct"]["steps_per_s"]
+        if "direct" in line and "direct_innov" in line:  # (timing class 2 brackets the solve and the innovation kernel as one launch)
+            line["innov_solve_ms_over_direct"] = line["direct_innov"]["solve_ms"] / line["direct"]["solve_ms"]
+            line["innov_steps_per_s_over_direct"] = line["direct_innov"]["steps_per_s"] / line["direct"]["steps_per_s"]
         if "direct_cross" in line:
             for m, tag in (("direct", "direct"), ("direct_smooth", "smooth")):
                 if m in line:
