@@ -33,17 +33,9 @@ __global__ void k_mhe_marginalize_early(DevCfg c, DevState s, int T);
     __global__ void NAME##_warm(DevCfg c, DevState s, int kstart, int K, int gws_len); \
     __global__ void NAME##_warm_pol(DevCfg c, DevState s, int kstart, int K, int gws_len);
 #include "solve_kernels.def"
-// the direct solve kernels (direct_kernels.def)
-#define DEKF_DIRECT_KERNEL(NAME, ...)                                               \
-    __global__ void NAME(DevCfg c, DevState s, int kstart, int K, double* cov);   \
-    __global__ void NAME##_smooth(DevCfg c, DevState s, int kstart, int K, double* cov, DirectWindow win); \
-    __global__ void NAME##_smooth_cross(DevCfg c, DevState s, int kstart, int K, double* cov, DirectWindow win, DirectCross cross); \
-    __global__ void NAME##_ep(DevCfg c, DevState s, int T, double* cov, const int* t0); \
-    __global__ void NAME##_smooth_ep(DevCfg c, DevState s, int T, double* cov, DirectWindow win, const int* t0); \
-    __global__ void NAME##_smooth_cross_ep(DevCfg c, DevState s, int T, double* cov, DirectWindow win, DirectCross cross, const int* t0); \
-    __global__ void NAME##_pp(DevState s, int T, double* cov, const int* t0, const DevCfg* pc); \
-    __global__ void NAME##_smooth_pp(DevState s, int T, double* cov, DirectWindow win, const int* t0, const DevCfg* pc); \
-    __global__ void NAME##_smooth_cross_pp(DevState s, int T, double* cov, DirectWindow win, DirectCross cross, const int* t0, const DevCfg* pc);
+// the direct solve kernels: every row of direct_kernels.def in every variant of its list
+#define DEKF_DIRECT_DECLARE_(SUFFIX, SMOOTH, CROSS, CLOCK, NAME) __global__ void NAME##SUFFIX(DEKF_DIRECT_PARAMS(SMOOTH, CROSS, CLOCK));
+#define DEKF_DIRECT_KERNEL(NAME, ...) DEKF_DIRECT_VARIANTS(DEKF_DIRECT_DECLARE_, NAME)
 #include "direct_kernels.def"
 // the innovation kernels behind the direct solve (mhe_innov_core.h), one per leg count, and their epoch twins
 #define DEKF_INNOV_KERNEL(L)                                                                                          \
@@ -140,32 +132,34 @@ struct dekf_handle_s {
     bool innov = false;
     InnovStore innov_st;
     bool innov_valid = false;
-    // dekf_reset_instances: the epochs of a direct handle (mhe_epoch_core.h).  ep_t0 | ep_c0: [B] ints each on the device, the handle's
-    // step and EKF tick count at every instance's last restart (0: never), allocated by the first call with a non-zero mask; t0_host:
-    // the host's copy of ep_t0 (dekf_get_instance_ticks, the window getters' steps), min_t0 its smallest entry; c0_host: the host's copy
-    // of ep_c0 (dekf_set_instance_params: an instance whose c0 is the handle's count has not ticked since its restart), folded with
-    // ep_c0.  epochs: a non-zero mask has been applied since dekf_create / dekf_reset — the handle launches the *_ep kernels, which
-    // take the two arrays
-    int *ep_t0 = nullptr, *ep_c0 = nullptr;
-    std::vector<int> t0_host, c0_host;
-    int min_t0 = 0;
-    bool epochs = false;
-    // dekf_set_active: pausing single instances (mhe_pause_core.h).  While instance b is paused the device's t0[b] and c0[b], and
-    // t0_host[b] and c0_host[b] with them, hold the sentinel, and pz_step[b] | pz_count[b] its next local step and local EKF count;
-    // act_host[b]: 1 runs, 0 is paused (all three allocated with the epochs).  min_t0 is then the smallest epoch of the active
-    // instances (the sentinel: none is) and max_frozen the largest local step at which a paused one stands (-1: none is paused).
-    // pausing: an instance has been paused since dekf_create / dekf_reset — the handle launches the *_act kernels, which skip one
-    std::vector<int> act_host, pz_step, pz_count;
-    int max_frozen = -1;
-    bool pausing = false;
-    // dekf_set_instance_params: the noise constants of every instance of a direct handle (mhe_params_core.h).  pp_mhe [B] DevCfg
-    // and pp_ekf [PpEkf::len][B] on the device, allocated by the first call that sets a table; inst_prm: the handle's parameters with
-    // every instance's noise fields (dekf_get_instance_params).  pp: the handle has a table: it launches the *_pp kernels, which are
-    // the epoch kernels with the table as one more argument, so the epoch arrays exist (all 0 unless `epochs`)
-    DevCfg* pp_mhe = nullptr;
-    double* pp_ekf = nullptr;
-    std::vector<dekf_params> inst_prm;
-    bool pp = false;
+    // The per-instance state of a direct handle: what dekf_reset_instances, dekf_set_active and dekf_set_instance_params keep.
+    struct Instances {
+        // dekf_reset_instances: the epochs (mhe_epoch_core.h).  t0 | c0: [B] ints each on the device (one block), the handle's step
+        // and EKF tick count at every instance's last restart (0: never); t0_host: the host's copy of t0 (dekf_get_instance_ticks,
+        // the window getters' steps); c0_host: the host's copy of c0 (dekf_set_instance_params: an instance whose c0 is the handle's
+        // count has not ticked since its restart), folded with c0.
+        int *t0 = nullptr, *c0 = nullptr;
+        std::vector<int> t0_host, c0_host;
+        // dekf_set_active: pausing single instances (mhe_pause_core.h).  While instance b is paused the device's t0[b] and c0[b], and
+        // t0_host[b] and c0_host[b] with them, hold the sentinel, and pz_step[b] | pz_count[b] its next local step and local EKF
+        // count; act_host[b]: 1 runs, 0 is paused.  min_t0: the smallest epoch of the active instances (the sentinel: none is);
+        // max_frozen: the largest local step at which a paused one stands (-1: none is paused) — bounds() keeps the two.
+        std::vector<int> act_host, pz_step, pz_count;
+        int min_t0 = 0, max_frozen = -1;
+        // dekf_set_instance_params: the noise constants of every instance (mhe_params_core.h).  pp_mhe [B] DevCfg and pp_ekf
+        // [PpEkf::len][B] on the device, allocated by the first call that sets a table; inst_prm: the handle's parameters with every
+        // instance's noise fields (dekf_get_instance_params)
+        DevCfg* pp_mhe = nullptr;
+        double* pp_ekf = nullptr;
+        std::vector<dekf_params> inst_prm;
+        // Since dekf_create / dekf_reset (read through instance_mode()): restarted, an instance has been restarted or paused; paused;
+        // table, the handle has a parameter table.  Invariants: paused implies restarted; restarted or table implies that ensure() has
+        // run, i.e. that the epoch arrays and the five host vectors exist (every epoch 0 and every instance active until `restarted`).
+        bool restarted = false, paused = false, table = false;
+        dekf_status ensure(dekf_handle_s* h);  // allocates the epoch arrays, all 0, at the first call that needs them
+        void bounds();                         // min_t0 and max_frozen from the host vectors
+        dekf_status clear(dekf_handle_s* h);   // dekf_reset: every epoch 0, nobody paused (pausing is state, not a setting); the table survives
+    } inst;
     size_t lds_solve = 0, lds_asm = 0, lds_kf = 0;
     int ekf_count = 0, pushes = 0, next_T = 0;
     bool initialized = false;
@@ -264,37 +258,35 @@ const SolveKernel* solve_kernel(SolveRole role, int L, int N) {
     return any;
 }
 
-// The direct solve kernels as dekf_set_solver selects them: every row of direct_kernels.def
-typedef void (*DirectFn)(DevCfg, DevState, int, int, double*);
-typedef void (*DirectSmoothFn)(DevCfg, DevState, int, int, double*, DirectWindow);
-typedef void (*DirectCrossFn)(DevCfg, DevState, int, int, double*, DirectWindow, DirectCross);
-typedef void (*DirectEpochFn)(DevCfg, DevState, int, double*, const int*);
-typedef void (*DirectSmoothEpochFn)(DevCfg, DevState, int, double*, DirectWindow, const int*);
-typedef void (*DirectCrossEpochFn)(DevCfg, DevState, int, double*, DirectWindow, DirectCross, const int*);
-typedef void (*DirectParamFn)(DevState, int, double*, const int*, const DevCfg*);
-typedef void (*DirectSmoothParamFn)(DevState, int, double*, DirectWindow, const int*, const DevCfg*);
-typedef void (*DirectCrossParamFn)(DevState, int, double*, DirectWindow, DirectCross, const int*, const DevCfg*);
-// the nine kernels of a row: the direct solve, its smoothing twin (dekf_set_smoother), the twin with the window cross-covariances
-// (dekf_set_window_cross), the epoch twins of the three (dekf_reset_instances) and the parameter twins of those (dekf_set_instance_params)
-enum DirectVariant { plain, smooth, cross, plain_ep, smooth_ep, cross_ep, plain_pp, smooth_pp, cross_pp };
+// The instance mode of a handle, which says which twin of every kernel it launches ("what a handle launches", below).  The clock is the
+// CLOCK of direct_kernels.def's variants.  WINDOW: uniform, the kernels of a handle without per-instance state.  EPOCH: an instance has
+// been restarted or paused — the *_ep kernels, every instance on its local step.  PARAM: the handle has a parameter table — the *_pp
+// kernels, the epoch kernels with the table as one more argument, with or without a restarted instance (`restarted`).
+// paused: an instance has been paused — the *_act kernels where there is one, which skip a paused instance.
+enum class Clock { WINDOW, EPOCH, PARAM };
+struct InstanceMode { Clock clock; bool restarted, paused; };
+InstanceMode instance_mode(const dekf_handle_s* h) {
+    const dekf_handle_s::Instances& i = h->inst;
+    return {i.table ? Clock::PARAM : (i.restarted ? Clock::EPOCH : Clock::WINDOW), i.restarted, i.paused};
+}
+
+// The direct solve kernels as dekf_set_solver selects them: every row of direct_kernels.def with the kernels of its variants
+// (DirectVariant: the list's entries; direct_variants[v]: SMOOTH, CROSS and the clock of entry v)
+#define DEKF_DIRECT_ENUM_(SUFFIX, ...) dv##SUFFIX,
+enum DirectVariant { DEKF_DIRECT_VARIANTS(DEKF_DIRECT_ENUM_) dv_count };
+struct DirectVariantInfo { bool smooth, cross; Clock clock; };
+#define DEKF_DIRECT_INFO_(SUFFIX, SMOOTH, CROSS, CLOCK, ...) {SMOOTH != 0, CROSS != 0, Clock::CLOCK},
+const DirectVariantInfo direct_variants[dv_count] = {DEKF_DIRECT_VARIANTS(DEKF_DIRECT_INFO_)};
 struct DirectKernel {
     int legs, ft, nfix;  // direct_solve_t's L and FT; the horizon the row is meant for (0: any)
-    DirectFn fn;
-    DirectSmoothFn fn_smooth;
-    DirectCrossFn fn_cross;
-    DirectEpochFn fn_ep;
-    DirectSmoothEpochFn fn_smooth_ep;
-    DirectCrossEpochFn fn_cross_ep;
-    DirectParamFn fn_pp;
-    DirectSmoothParamFn fn_smooth_pp;
-    DirectCrossParamFn fn_cross_pp;
-    const char* name[9];  // by DirectVariant
+#define DEKF_DIRECT_FIELD_(SUFFIX, SMOOTH, CROSS, CLOCK, ...) void (*fn##SUFFIX)(DEKF_DIRECT_PARAMS(SMOOTH, CROSS, CLOCK));
+    DEKF_DIRECT_VARIANTS(DEKF_DIRECT_FIELD_)  // fn, fn_smooth, ...: every variant's kernel with its own signature
+    const char* name[dv_count];  // by DirectVariant
 };
-#define DEKF_DIRECT_KERNEL(NAME, L, FT, NFIX)                                                                                \
-    {L, FT, NFIX, NAME, NAME##_smooth, NAME##_smooth_cross, NAME##_ep, NAME##_smooth_ep, NAME##_smooth_cross_ep,              \
-     NAME##_pp, NAME##_smooth_pp, NAME##_smooth_cross_pp,                                                                    \
-     {#NAME, #NAME "_smooth", #NAME "_smooth_cross", #NAME "_ep", #NAME "_smooth_ep", #NAME "_smooth_cross_ep",              \
-      #NAME "_pp", #NAME "_smooth_pp", #NAME "_smooth_cross_pp"}},
+#define DEKF_DIRECT_FN_(SUFFIX, SMOOTH, CROSS, CLOCK, NAME) NAME##SUFFIX,
+#define DEKF_DIRECT_NAME_(SUFFIX, SMOOTH, CROSS, CLOCK, NAME) #NAME #SUFFIX,
+#define DEKF_DIRECT_KERNEL(NAME, L, FT, NFIX) \
+    {L, FT, NFIX, DEKF_DIRECT_VARIANTS(DEKF_DIRECT_FN_, NAME) {DEKF_DIRECT_VARIANTS(DEKF_DIRECT_NAME_, NAME)}},
 const DirectKernel direct_kernels[] = {
 #include "direct_kernels.def"
 };
@@ -317,12 +309,15 @@ struct InnovKernel { InnovFn fn; InnovEpochFn fn_ep; };
 const InnovKernel innov_kernels[DEKF_MAX_LEGS] = {{k_mhe_innov_1, k_mhe_innov_1_ep}, {k_mhe_innov_2, k_mhe_innov_2_ep},
                                                   {k_mhe_innov_3, k_mhe_innov_3_ep}, {k_mhe_innov_4, k_mhe_innov_4_ep}};
 
-// the kernel of its row that a direct handle launches: the smoother and cross settings pick the twin, and a handle that has restarted
-// an instance (epochs) launches the epoch twin of that one, which finds every instance's window from the step; a handle with a
-// parameter table (pp) the parameter twin of the epoch twin, with or without a restarted instance
+// the kernel of its row that a direct handle launches: the variant of the list with the handle's smoother and cross settings and the
+// clock of its instance mode
 DirectVariant direct_variant(const dekf_handle_s* h) {
-    const int v = !h->smoother ? plain : (h->cross ? cross : smooth);
-    return (DirectVariant)(h->pp ? v + plain_pp : (h->epochs ? v + plain_ep : v));
+    const Clock clock = instance_mode(h).clock;
+    const bool cross = h->smoother && h->cross;  // (the cross-covariances are the smoother's)
+    for (int v = 0; v < dv_count; ++v)
+        if (direct_variants[v].smooth == h->smoother && direct_variants[v].cross == cross && direct_variants[v].clock == clock)
+            return (DirectVariant)v;
+    return dv_count;  // (not reached: the list has every clock with and without the smoother and its cross-covariances)
 }
 
 // The solve launch of a step with a window of K steps: what dekf_update launches, dekf_solve_kernel_name names and dekf_launch_info
@@ -333,19 +328,21 @@ struct SolveLaunch {
     SolveFn admm;           // the ADMM kernel; null on a direct handle, which launches ...
     DirectVariant variant;  // ... this kernel of its row (h->direct)
     // ... and behind it, on an innovation handle (dekf_set_innovation), the innovation kernel of its leg count (null: none): the epoch
-    // twin where the direct kernel is an epoch or parameter twin.  One wavefront per instance, a grid of B, lds_innov of LDS
+    // twin where the direct kernel's clock is not WINDOW (there is no parameter twin).  One wavefront per instance, a grid of B,
+    // lds_innov of LDS
     const InnovKernel* innov;
     size_t lds_innov;
 };
 SolveLaunch solve_launch(const dekf_handle_s* h, int K) {
-    const DirectVariant v = direct_variant(h);
-    if (h->solver == DEKF_SOLVER_DIRECT)
+    if (h->solver == DEKF_SOLVER_DIRECT) {
+        const DirectVariant v = direct_variant(h);
         return {h->direct->name[v], h->c.B, 64, h->lds_direct, nullptr, v, h->innov ? &innov_kernels[h->c.L - 1] : nullptr,
                 (size_t)InnovScratch::len(h->c.L) * sizeof(double)};
+    }
     const bool full = h->solve_entry_full && K == h->c.N;
     const SolveTwin t = solve_twin(full ? h->solve_entry_full : h->solve_entry, h->c.polish != 0, h->c.warm != 0);
-    if (full) return {t.name, h->solve_grid_full, h->solve_threads_full, h->lds_solve_full, t.fn, v, nullptr, 0};
-    return {t.name, h->solve_grid, DEKF_SOLVE_THREADS, h->lds_solve, t.fn, v, nullptr, 0};
+    if (full) return {t.name, h->solve_grid_full, h->solve_threads_full, h->lds_solve_full, t.fn, dv_count, nullptr, 0};
+    return {t.name, h->solve_grid, DEKF_SOLVE_THREADS, h->lds_solve, t.fn, dv_count, nullptr, 0};
 }
 
 // A family of full-window kernels (K == N): the shapes it covers are the rows of its role in solve_kernels.def
@@ -487,35 +484,6 @@ dekf_status quiesce(dekf_handle h) {
     return DEKF_OK;
 }
 
-// the epoch arrays of a direct handle (t0 | c0 in one block, all 0), allocated by the first call that needs them
-dekf_status ensure_epochs(dekf_handle h) {
-    if (h->ep_t0) return DEKF_OK;
-    const size_t B = (size_t)h->c.B;
-    int* e = nullptr;
-    TRY(dev_alloc(h, 2 * B * sizeof(int), &e));
-    HIPCHK(hipMemsetAsync(e, 0, 2 * B * sizeof(int), h->stream));
-    h->ep_t0 = e;
-    h->ep_c0 = e + B;
-    h->t0_host.assign(B, 0);
-    h->c0_host.assign(B, 0);
-    h->act_host.assign(B, 1);
-    h->pz_step.assign(B, 0);
-    h->pz_count.assign(B, 0);
-    h->min_t0 = 0;
-    h->max_frozen = -1;
-    return DEKF_OK;
-}
-
-// what the window getters' steps take from the epochs: the smallest one of the active instances, the largest frozen local step
-void epoch_bounds(dekf_handle h) {
-    h->min_t0 = DEKF_EPOCH_PAUSED;
-    h->max_frozen = -1;
-    for (size_t b = 0; b < h->t0_host.size(); ++b) {
-        if (h->act_host[b]) { if (h->t0_host[b] < h->min_t0) h->min_t0 = h->t0_host[b]; }
-        else if (h->pz_step[b] - 1 > h->max_frozen) h->max_frozen = h->pz_step[b] - 1;
-    }
-}
-
 struct Timed {  // brackets one launch with events when timing is on
     dekf_handle h;
     int cls;
@@ -553,44 +521,97 @@ MheStep mhe_step(dekf_handle h, int T) {
     return st;
 }
 
+// What a handle launches: one function per launch, which picks the twin of the handle's instance mode; the caller checks
+// hipGetLastError.  Where the kernels are asymmetric the functions are: no *_act marginalise or solve kernel (the epoch and parameter
+// twins do nothing for a paused instance), no *_pp innovation, latch or fold kernel (those read no noise constants).
+// ... the launch that solve_launch describes, on stream ss
+void launch_solve(dekf_handle h, const SolveLaunch& l, const DevState& sp, int T, int kstart, int K, hipStream_t ss) {
+    if (l.admm) return (void)l.admm<<<l.grid, l.threads, l.lds, ss>>>(h->c, sp, kstart, K, h->gws_len);
+    const DirectKernel& d = *h->direct;
+    // the arguments of a variant, in the order of DEKF_DIRECT_PARAMS: the clock's head, cov, [win], [cross], the clock's tail
+#define DEKF_DIRECT_HEADARG_WINDOW h->c, sp, kstart, K
+#define DEKF_DIRECT_TAILARG_WINDOW
+#define DEKF_DIRECT_HEADARG_EPOCH h->c, sp, T
+#define DEKF_DIRECT_TAILARG_EPOCH , h->inst.t0
+#define DEKF_DIRECT_HEADARG_PARAM sp, T
+#define DEKF_DIRECT_TAILARG_PARAM , h->inst.t0, h->inst.pp_mhe
+#define DEKF_DIRECT_LAUNCH_(SUFFIX, SMOOTH, CROSS, CLOCK, ...)                                                         \
+    case dv##SUFFIX:                                                                                                   \
+        d.fn##SUFFIX<<<l.grid, l.threads, l.lds, ss>>>(DEKF_DIRECT_HEADARG_##CLOCK, h->mhe_cov DEKF_DIRECT_IF_##SMOOTH(, h->win) \
+                                                       DEKF_DIRECT_IF_##CROSS(, h->cross_st) DEKF_DIRECT_TAILARG_##CLOCK); \
+        break;
+    switch (l.variant) {
+    DEKF_DIRECT_VARIANTS(DEKF_DIRECT_LAUNCH_)
+    case dv_count: break;
+    }
+    if (!l.innov) return;
+    // (an innovation handle: the statistics of the newest step from what the solve just left, in stream order behind it)
+    if (direct_variants[l.variant].clock == Clock::WINDOW) l.innov->fn<<<l.grid, 64, l.lds_innov, ss>>>(h->c, sp, kstart, K, h->mhe_cov, h->innov_st);
+    else l.innov->fn_ep<<<l.grid, 64, l.lds_innov, ss>>>(h->c, sp, T, h->mhe_cov, h->innov_st, h->inst.t0);
+}
+// ... the EKF tick (dekf_ekf_step)
+void launch_tick(dekf_handle h) {
+    const InstanceMode m = instance_mode(h);
+    const int grid = (h->c.B + 63) / 64;
+    if (m.clock == Clock::WINDOW) k_ekf_tick<<<grid, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count);
+    else if (m.clock == Clock::EPOCH && !m.paused) k_ekf_tick_ep<<<grid, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count, h->inst.c0);
+    else if (m.clock == Clock::EPOCH) k_ekf_tick_act<<<grid, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count, h->inst.c0);
+    else if (!m.paused) k_ekf_tick_pp<<<grid, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count, h->inst.c0, h->inst.pp_ekf);
+    else k_ekf_tick_act_pp<<<grid, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count, h->inst.c0, h->inst.pp_ekf);
+}
+// ... the terms of step T into sp (dekf_initialize of a handle with a table: T = 0, pushes = 0, the initialise path on every instance's own prior)
+void launch_assemble(dekf_handle h, const DevState& sp, int T, int pushes) {
+    const InstanceMode m = instance_mode(h);
+    if (m.clock == Clock::WINDOW) k_mhe_assemble<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->c, sp, T, pushes);
+    else if (m.clock == Clock::EPOCH && !m.paused) k_mhe_assemble_ep<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->c, sp, T, pushes, h->inst.t0);
+    else if (m.clock == Clock::EPOCH) k_mhe_assemble_act<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->c, sp, T, pushes, h->inst.t0);
+    else if (!m.paused) k_mhe_assemble_pp<<<h->c.B, 64, h->lds_asm, h->stream>>>(sp, T, pushes, h->inst.t0, h->inst.pp_mhe);
+    else k_mhe_assemble_act_pp<<<h->c.B, 64, h->lds_asm, h->stream>>>(sp, T, pushes, h->inst.t0, h->inst.pp_mhe);
+}
+// ... the arrival cost of step T ahead of time, on the early stream (marginalize_next_early)
+void launch_marginalize_early(dekf_handle h, int T) {
+    switch (instance_mode(h).clock) {
+    case Clock::WINDOW: k_mhe_marginalize_early<<<h->c.B, 64, h->lds_asm, h->early_stream>>>(h->c, h->s, T); break;
+    case Clock::EPOCH: k_mhe_marginalize_early_ep<<<h->c.B, 64, h->lds_asm, h->early_stream>>>(h->c, h->s, T, h->inst.t0); break;
+    case Clock::PARAM: k_mhe_marginalize_early_pp<<<h->c.B, 64, h->lds_asm, h->early_stream>>>(h->s, T, h->inst.t0, h->inst.pp_mhe); break;
+    }
+}
+// ... the VO latch (dekf_push_vo; device pointers): a sample for a paused instance is dropped
+void launch_latch_vo(dekf_handle h, const int* mask, const double* t_pre, const double* t_now, const double* dp, const double* t_pose,
+                     const double* q_vo) {
+    const int grid = (h->c.B + 255) / 256;
+    if (instance_mode(h).paused) k_latch_vo_act<<<grid, 256, 0, h->stream>>>(h->c, h->s, mask, h->inst.t0, t_pre, t_now, dp, t_pose, q_vo);
+    else k_latch_vo<<<grid, 256, 0, h->stream>>>(h->c, h->s, mask, t_pre, t_now, dp, t_pose, q_vo);
+}
+// ... the fold of the device's epochs with the host's EKF tick count (dekf_ekf_step): the sentinel of a paused instance stays
+void launch_fold(dekf_handle h, int count_old, int count_new) {
+    const int grid = (h->c.B + 255) / 256;
+    if (instance_mode(h).paused) k_fold_epochs_act<<<grid, 256, 0, h->stream>>>(h->inst.c0, h->c.B, count_old, count_new, h->c.ekf_hist);
+    else k_fold_epochs<<<grid, 256, 0, h->stream>>>(h->inst.c0, h->c.B, count_old, count_new, h->c.ekf_hist);
+}
+// ... the initial state of every instance of set sp (dekf_reset): with a table every instance's own, and the table survives
+void launch_reset_state(dekf_handle h, const DevState& sp) {
+    const int grid = (h->c.B + 255) / 256;
+    if (instance_mode(h).clock == Clock::PARAM) k_reset_state_pp<<<grid, 256, 0, h->stream>>>(h->c, sp, h->inst.pp_ekf);
+    else k_reset_state<<<grid, 256, 0, h->stream>>>(h->c, sp);
+}
+// ... the restart of the instances of a device mask: with a table every instance's own initial EKF state; the innovation stores' entries NaN, as cov
+void launch_reset_instances(dekf_handle h, const int* dmask) {
+    const int grid = (h->c.B + 255) / 256;
+    if (instance_mode(h).clock == Clock::PARAM)
+        k_reset_instances_pp<<<grid, 256, 0, h->stream>>>(h->c, h->s, dmask, h->mhe_cov, h->inst.t0, h->inst.c0, h->next_T, h->ekf_count, h->inst.pp_ekf);
+    else k_reset_instances<<<grid, 256, 0, h->stream>>>(h->c, h->s, dmask, h->mhe_cov, h->inst.t0, h->inst.c0, h->next_T, h->ekf_count);
+    if (h->innov_st.nu) k_innov_nan<<<grid, 256, 0, h->stream>>>(h->c, dmask, h->innov_st);
+}
+
 // the terms of step T: waits for the snapshot copy to be free and for the arrival cost computed ahead, then the assemble
 dekf_status assemble_step(dekf_handle h, const MheStep& st) {
     if (h->pipelined && h->snap_busy[st.snap_set]) HIPCHK(hipStreamWaitEvent(h->stream, h->ev_snap_free[st.snap_set], 0));
     if (h->early_pending) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_early_done, 0)); h->early_pending = false; }
-    {
-        Timed t(h, 1);
-        if (h->pausing && h->pp) k_mhe_assemble_act_pp<<<h->c.B, 64, h->lds_asm, h->stream>>>(st.sp, st.T, h->pushes, h->ep_t0, h->pp_mhe);
-        else if (h->pausing) k_mhe_assemble_act<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->c, st.sp, st.T, h->pushes, h->ep_t0);
-        else if (h->pp) k_mhe_assemble_pp<<<h->c.B, 64, h->lds_asm, h->stream>>>(st.sp, st.T, h->pushes, h->ep_t0, h->pp_mhe);
-        else if (h->epochs) k_mhe_assemble_ep<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->c, st.sp, st.T, h->pushes, h->ep_t0);
-        else k_mhe_assemble<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->c, st.sp, st.T, h->pushes);
-    }
+    { Timed t(h, 1); launch_assemble(h, st.sp, st.T, h->pushes); }
     HIPCHK(hipGetLastError());
     if (h->early_stream) HIPCHK(hipEventRecord(h->ev_asm_done, h->stream));
     return DEKF_OK;
-}
-
-// the launch that solve_launch describes, on stream ss
-void launch_solve(dekf_handle h, const SolveLaunch& l, const DevState& sp, int T, int kstart, int K, hipStream_t ss) {
-    if (l.admm) return (void)l.admm<<<l.grid, l.threads, l.lds, ss>>>(h->c, sp, kstart, K, h->gws_len);
-    const DirectKernel& d = *h->direct;
-    switch (l.variant) {
-    case plain: d.fn<<<l.grid, l.threads, l.lds, ss>>>(h->c, sp, kstart, K, h->mhe_cov); break;
-    case smooth: d.fn_smooth<<<l.grid, l.threads, l.lds, ss>>>(h->c, sp, kstart, K, h->mhe_cov, h->win); break;
-    case cross: d.fn_cross<<<l.grid, l.threads, l.lds, ss>>>(h->c, sp, kstart, K, h->mhe_cov, h->win, h->cross_st); break;
-    // (a direct handle that has restarted an instance: the epoch twins, which find every instance's window from the step)
-    case plain_ep: d.fn_ep<<<l.grid, l.threads, l.lds, ss>>>(h->c, sp, T, h->mhe_cov, h->ep_t0); break;
-    case smooth_ep: d.fn_smooth_ep<<<l.grid, l.threads, l.lds, ss>>>(h->c, sp, T, h->mhe_cov, h->win, h->ep_t0); break;
-    case cross_ep: d.fn_cross_ep<<<l.grid, l.threads, l.lds, ss>>>(h->c, sp, T, h->mhe_cov, h->win, h->cross_st, h->ep_t0); break;
-    // (a direct handle with a parameter table: the parameter twins, the epoch twins with every instance's row of the table)
-    case plain_pp: d.fn_pp<<<l.grid, l.threads, l.lds, ss>>>(sp, T, h->mhe_cov, h->ep_t0, h->pp_mhe); break;
-    case smooth_pp: d.fn_smooth_pp<<<l.grid, l.threads, l.lds, ss>>>(sp, T, h->mhe_cov, h->win, h->ep_t0, h->pp_mhe); break;
-    case cross_pp: d.fn_cross_pp<<<l.grid, l.threads, l.lds, ss>>>(sp, T, h->mhe_cov, h->win, h->cross_st, h->ep_t0, h->pp_mhe); break;
-    }
-    if (!l.innov) return;
-    // (an innovation handle: the statistics of the newest step from what the solve just left, in stream order behind it)
-    if (l.variant >= plain_ep) l.innov->fn_ep<<<l.grid, 64, l.lds_innov, ss>>>(h->c, sp, T, h->mhe_cov, h->innov_st, h->ep_t0);
-    else l.innov->fn<<<l.grid, 64, l.lds_innov, ss>>>(h->c, sp, kstart, K, h->mhe_cov, h->innov_st);
 }
 
 // the solve of step T behind its terms, and what the getters need to know about it
@@ -628,9 +649,9 @@ dekf_status solve_step(dekf_handle h, const MheStep& st) {
     h->mhe_cov_valid = h->solver == DEKF_SOLVER_DIRECT;
     h->innov_valid = h->innov;
     h->win_steps = h->smoother ? K : 0;
-    if (h->epochs && h->smoother) {  // the largest window of the batch: the instance restarted longest ago (none at its local step 0),
-        const int Ta = T - h->min_t0;  // or a paused one with the window it stands at
-        const int Tl = Ta > h->max_frozen ? Ta : h->max_frozen;
+    if (instance_mode(h).restarted && h->smoother) {  // the largest window of the batch: the instance restarted longest ago (none at its local step 0),
+        const int Ta = T - h->inst.min_t0;  // or a paused one with the window it stands at
+        const int Tl = Ta > h->inst.max_frozen ? Ta : h->inst.max_frozen;
         h->win_steps = Tl < 1 ? 0 : (Tl + 1 < h->c.N ? Tl + 1 : h->c.N);
     }
     return DEKF_OK;
@@ -641,16 +662,83 @@ dekf_status solve_step(dekf_handle h, const MheStep& st) {
 dekf_status marginalize_next_early(dekf_handle h, int T) {
     HIPCHK(hipStreamWaitEvent(h->early_stream, h->ev_asm_done, 0));
     HIPCHK(hipEventRecord(h->ev_early_mark, h->early_stream));  // (as before a pipelined solve launch: see there)
-    if (h->pp) k_mhe_marginalize_early_pp<<<h->c.B, 64, h->lds_asm, h->early_stream>>>(h->s, T + 1, h->ep_t0, h->pp_mhe);
-    else if (h->epochs) k_mhe_marginalize_early_ep<<<h->c.B, 64, h->lds_asm, h->early_stream>>>(h->c, h->s, T + 1, h->ep_t0);
-    else k_mhe_marginalize_early<<<h->c.B, 64, h->lds_asm, h->early_stream>>>(h->c, h->s, T + 1);
+    launch_marginalize_early(h, T + 1);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev_early_done, h->early_stream));
     h->early_pending = true;
     return DEKF_OK;
 }
 
+// The per-instance entry points' common ground: fn needs an in-order direct MHE handle, and with need_init an initialised one; fn's
+// [B] mask (read_mask); [B] ints to the caller's host or device memory (deliver_ints)
+dekf_status need_direct(dekf_handle h, const char* fn, bool need_init) {
+    const std::string f(fn);
+    if (h->c.est_type != 0) return fail(DEKF_ERR_INVALID, (f + " needs a direct MHE handle: this is a KF handle (est_type 1)").c_str());
+    if (h->pipelined) return fail(DEKF_ERR_INVALID, (f + " cannot be combined with solve_pipeline = 1").c_str());
+    if (h->solver != DEKF_SOLVER_DIRECT) return fail(DEKF_ERR_INVALID, (f + " needs a direct handle (dekf_set_solver(h, DEKF_SOLVER_DIRECT))").c_str());
+    if (need_init && !h->initialized) return fail(DEKF_ERR_ORDER, (f + " before dekf_initialize").c_str());
+    return DEKF_OK;
+}
+// (the host reads the mask: it refuses values other than 0 and 1 and keeps the books.  A device mask costs a copy and a wait here;
+// restarts and pauses are rare, and the call between two ticks is not on the hot path)
+dekf_status read_mask(dekf_handle h, const char* fn, const int* mask, dekf_mem where, std::vector<int>& m) {
+    const size_t B = (size_t)h->c.B;
+    m.resize(B);
+    if (where == DEKF_HOST) std::memcpy(m.data(), mask, B * sizeof(int));
+    else {
+        HIPCHK(hipMemcpyAsync(m.data(), mask, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    for (size_t b = 0; b < B; ++b)
+        if (m[b] != 0 && m[b] != 1) return fail(DEKF_ERR_INVALID, (std::string(fn) + ": mask entries must be 0 or 1").c_str());
+    return DEKF_OK;
+}
+dekf_status deliver_ints(dekf_handle h, int* dst, const std::vector<int>& v, dekf_mem where) {
+    if (where == DEKF_HOST) std::memcpy(dst, v.data(), v.size() * sizeof(int));
+    else {
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipMemcpyAsync(dst, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));  // (v is the caller's local)
+    }
+    return DEKF_OK;
+}
+
 }  // namespace
+
+// the epoch arrays of a direct handle (t0 | c0 in one block, all 0), allocated by the first call that needs them
+dekf_status dekf_handle_s::Instances::ensure(dekf_handle h) {
+    if (t0) return DEKF_OK;
+    const size_t B = (size_t)h->c.B;
+    TRY(dev_alloc(h, 2 * B * sizeof(int), &t0));
+    c0 = t0 + B;
+    pz_step.assign(B, 0);
+    pz_count.assign(B, 0);
+    return clear(h);
+}
+
+// what the window getters' steps take from the epochs: the smallest one of the active instances, the largest frozen local step
+void dekf_handle_s::Instances::bounds() {
+    min_t0 = DEKF_EPOCH_PAUSED;
+    max_frozen = -1;
+    for (size_t b = 0; b < t0_host.size(); ++b) {
+        if (act_host[b]) { if (t0_host[b] < min_t0) min_t0 = t0_host[b]; }
+        else if (pz_step[b] - 1 > max_frozen) max_frozen = pz_step[b] - 1;
+    }
+}
+
+// every epoch 0 and nobody paused: the handle launches the kernels of a handle that never restarted an instance again
+dekf_status dekf_handle_s::Instances::clear(dekf_handle h) {
+    if (!t0) return DEKF_OK;
+    const size_t B = (size_t)h->c.B;
+    HIPCHK(hipMemsetAsync(t0, 0, 2 * B * sizeof(int), h->stream));
+    t0_host.assign(B, 0);
+    c0_host.assign(B, 0);
+    act_host.assign(B, 1);
+    min_t0 = 0;
+    max_frozen = -1;
+    restarted = paused = false;
+    return DEKF_OK;
+}
 
 extern "C" {
 
@@ -851,8 +939,7 @@ dekf_status dekf_reset(dekf_handle h) {
     TRY(quiesce(h));
     for (int i = 0; i < DEKF_SNAP_SETS; ++i) h->snap_busy[i] = false;  // (every solve is behind the events just waited for)
     for (int i = 0; i < (h->pipelined ? 2 : 1); ++i) {
-        if (h->pp) k_reset_state_pp<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->sp[i], h->pp_ekf);  // (the table survives)
-        else k_reset_state<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->sp[i]);
+        launch_reset_state(h, h->sp[i]);
         HIPCHK(hipGetLastError());
     }
     h->last_par = h->ekf_count = h->pushes = h->next_T = 0;
@@ -862,147 +949,98 @@ dekf_status dekf_reset(dekf_handle h) {
     if (h->innov_st.nu)  // every entry NaN again (all bits set is one): an instance keeps it until its first solve
         HIPCHK(hipMemsetAsync(h->innov_st.nu, 0xff, (size_t)h->c.B * InnovStore::len(h->c.L) * sizeof(double), h->stream));
     h->win_steps = 0;
-    if (h->ep_t0) {  // every epoch: the handle launches the kernels of a handle that never restarted an instance again
-        HIPCHK(hipMemsetAsync(h->ep_t0, 0, 2 * (size_t)h->c.B * sizeof(int), h->stream));
-        h->t0_host.assign((size_t)h->c.B, 0);
-        h->c0_host.assign((size_t)h->c.B, 0);
-        h->act_host.assign((size_t)h->c.B, 1);  // (pausing is state, not a setting: a reset handle is a fresh handle)
-        h->min_t0 = 0;
-        h->max_frozen = -1;
-        h->epochs = h->pausing = false;
-    }
+    TRY(h->inst.clear(h));
     return DEKF_OK;
 }
 
 dekf_status dekf_reset_instances(dekf_handle h, const int* mask, dekf_mem where) {
     if (!h) return fail(DEKF_ERR_INVALID, "null handle");
     if (!mask) return fail(DEKF_ERR_INVALID, "null mask");
-    if (h->c.est_type != 0) return fail(DEKF_ERR_INVALID, "dekf_reset_instances needs a direct MHE handle: this is a KF handle (est_type 1)");
-    if (h->pipelined) return fail(DEKF_ERR_INVALID, "dekf_reset_instances cannot be combined with solve_pipeline = 1");
-    if (h->solver != DEKF_SOLVER_DIRECT) return fail(DEKF_ERR_INVALID, "dekf_reset_instances needs a direct handle (dekf_set_solver(h, DEKF_SOLVER_DIRECT))");
-    if (!h->initialized) return fail(DEKF_ERR_ORDER, "dekf_reset_instances before dekf_initialize");
+    TRY(need_direct(h, "dekf_reset_instances", true));
     HIPCHK(hipSetDevice(h->device));
     const size_t B = (size_t)h->c.B;
-    // the host reads the mask: it refuses values other than 0 and 1, and it keeps its own copy of the epochs (a device mask costs a
-    // copy and a wait here; restarts are rare, and the call between two ticks is not on the hot path)
-    std::vector<int> m(B);
-    if (where == DEKF_HOST) std::memcpy(m.data(), mask, B * sizeof(int));
-    else {
-        HIPCHK(hipMemcpyAsync(m.data(), mask, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
+    dekf_handle_s::Instances& in = h->inst;
+    std::vector<int> m;
+    TRY(read_mask(h, "dekf_reset_instances", mask, where, m));
     bool any = false;
-    for (size_t b = 0; b < B; ++b) {
-        if (m[b] != 0 && m[b] != 1) return fail(DEKF_ERR_INVALID, "dekf_reset_instances: mask entries must be 0 or 1");
-        any = any || m[b] == 1;
-    }
+    for (size_t b = 0; b < B; ++b) any = any || m[b] == 1;
     if (!any) return DEKF_OK;  // nothing changes, the kernels the handle launches included
     TRY(quiesce(h));  // (what dekf_reset waits for)
-    TRY(ensure_epochs(h));
+    TRY(in.ensure(h));
     const int* dmask = where == DEKF_HOST ? m.data() : mask;
     if (where == DEKF_HOST) {
         TRY(ensure_stage(h, B * sizeof(int)));
         TRY(stage_in(h, 0, &dmask, B));
     }
-    if (h->pp)  // (every instance's own initial EKF state)
-        k_reset_instances_pp<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->s, dmask, h->mhe_cov, h->ep_t0, h->ep_c0, h->next_T, h->ekf_count, h->pp_ekf);
-    else k_reset_instances<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->s, dmask, h->mhe_cov, h->ep_t0, h->ep_c0, h->next_T, h->ekf_count);
-    if (h->innov_st.nu) k_innov_nan<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, dmask, h->innov_st);  // (NaN until its first solve, as cov)
+    launch_reset_instances(h, dmask);
     HIPCHK(hipGetLastError());
     if (where == DEKF_HOST) HIPCHK(hipStreamSynchronize(h->stream));  // (m, a local, is the source of the copy)
     for (size_t b = 0; b < B; ++b)  // (a paused instance that is restarted is active: its new life starts here)
-        if (m[b]) restart_instance((int)b, h->act_host.data(), h->t0_host.data(), h->c0_host.data(), h->next_T, h->ekf_count);
-    epoch_bounds(h);
-    h->epochs = true;
+        if (m[b]) restart_instance((int)b, in.act_host.data(), in.t0_host.data(), in.c0_host.data(), h->next_T, h->ekf_count);
+    in.bounds();
+    in.restarted = true;
     return DEKF_OK;
 }
 
 dekf_status dekf_get_instance_ticks(dekf_handle h, int* ticks, dekf_mem where) {
     if (!h || !ticks) return fail(DEKF_ERR_INVALID, "null argument");
     if (!h->initialized) return fail(DEKF_ERR_ORDER, "dekf_get_instance_ticks before dekf_initialize");
-    const size_t B = (size_t)h->c.B;
+    const dekf_handle_s::Instances& in = h->inst;
     const int T = h->next_T - 1;  // the step of the last update (0: dekf_initialize)
-    std::vector<int> t(B, T);
-    if (h->epochs)
-        for (size_t b = 0; b < B; ++b) t[b] = instance_tick((int)b, T, h->act_host.data(), h->pz_step.data(), h->t0_host.data());
-    if (where == DEKF_HOST) std::memcpy(ticks, t.data(), B * sizeof(int));
-    else {
-        HIPCHK(hipSetDevice(h->device));
-        HIPCHK(hipMemcpyAsync(ticks, t.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));  // (t is a local)
-    }
-    return DEKF_OK;
+    std::vector<int> t((size_t)h->c.B, T);
+    if (instance_mode(h).restarted)
+        for (size_t b = 0; b < t.size(); ++b) t[b] = instance_tick((int)b, T, in.act_host.data(), in.pz_step.data(), in.t0_host.data());
+    return deliver_ints(h, ticks, t, where);
 }
 
 dekf_status dekf_set_active(dekf_handle h, const int* active, dekf_mem where) {
     if (!h) return fail(DEKF_ERR_INVALID, "null handle");
     if (!active) return fail(DEKF_ERR_INVALID, "null mask");
-    if (h->c.est_type != 0) return fail(DEKF_ERR_INVALID, "dekf_set_active needs a direct MHE handle: this is a KF handle (est_type 1)");
-    if (h->pipelined) return fail(DEKF_ERR_INVALID, "dekf_set_active cannot be combined with solve_pipeline = 1");
-    if (h->solver != DEKF_SOLVER_DIRECT) return fail(DEKF_ERR_INVALID, "dekf_set_active needs a direct handle (dekf_set_solver(h, DEKF_SOLVER_DIRECT))");
-    if (!h->initialized) return fail(DEKF_ERR_ORDER, "dekf_set_active before dekf_initialize");
+    TRY(need_direct(h, "dekf_set_active", true));
     HIPCHK(hipSetDevice(h->device));
     const size_t B = (size_t)h->c.B;
-    // the host reads the mask, as dekf_reset_instances does: it refuses values other than 0 and 1 and keeps the books of the pauses
-    std::vector<int> m(B);
-    if (where == DEKF_HOST) std::memcpy(m.data(), active, B * sizeof(int));
-    else {
-        HIPCHK(hipMemcpyAsync(m.data(), active, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
+    dekf_handle_s::Instances& in = h->inst;
+    std::vector<int> m;
+    TRY(read_mask(h, "dekf_set_active", active, where, m));
     bool change = false;
-    for (size_t b = 0; b < B; ++b) {
-        if (m[b] != 0 && m[b] != 1) return fail(DEKF_ERR_INVALID, "dekf_set_active: mask entries must be 0 or 1");
-        change = change || m[b] != (h->ep_t0 ? h->act_host[b] : 1);
-    }
+    for (size_t b = 0; b < B; ++b) change = change || m[b] != (in.t0 ? in.act_host[b] : 1);
     if (!change) return DEKF_OK;  // the mask the handle has: nothing changes, the kernels it launches included
     TRY(quiesce(h));  // (what dekf_reset_instances waits for: the arrival cost computed ahead reads the epochs)
-    TRY(ensure_epochs(h));
+    TRY(in.ensure(h));
     for (size_t b = 0; b < B; ++b)
-        set_active_instance((int)b, m[b], h->act_host.data(), h->pz_step.data(), h->pz_count.data(), h->t0_host.data(), h->c0_host.data(),
+        set_active_instance((int)b, m[b], in.act_host.data(), in.pz_step.data(), in.pz_count.data(), in.t0_host.data(), in.c0_host.data(),
                             h->next_T, h->ekf_count, h->c.ekf_hist);
-    HIPCHK(hipMemcpyAsync(h->ep_t0, h->t0_host.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->ep_c0, h->c0_host.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(in.t0, in.t0_host.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(in.c0, in.c0_host.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));  // (the host's copies change at the next call)
-    epoch_bounds(h);
-    h->epochs = true;
-    h->pausing = true;  // (a change on a handle that has paused nobody is a pause)
+    in.bounds();
+    in.restarted = in.paused = true;  // (a change on a handle that has paused nobody is a pause)
     return DEKF_OK;
 }
 
 dekf_status dekf_get_active(dekf_handle h, int* active, dekf_mem where) {
     if (!h || !active) return fail(DEKF_ERR_INVALID, "null argument");
     if (!h->initialized) return fail(DEKF_ERR_ORDER, "dekf_get_active before dekf_initialize");
-    const size_t B = (size_t)h->c.B;
-    std::vector<int> a(B, 1);
-    if (h->pausing) a = h->act_host;
-    if (where == DEKF_HOST) std::memcpy(active, a.data(), B * sizeof(int));
-    else {
-        HIPCHK(hipSetDevice(h->device));
-        HIPCHK(hipMemcpyAsync(active, a.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));  // (a is a local)
-    }
-    return DEKF_OK;
+    return deliver_ints(h, active, instance_mode(h).paused ? h->inst.act_host : std::vector<int>((size_t)h->c.B, 1), where);
 }
 
 dekf_status dekf_set_instance_params(dekf_handle h, const dekf_params* sets, int nsets, const int* set_of) {
     if (!h) return fail(DEKF_ERR_INVALID, "null handle");
-    if (h->c.est_type != 0) return fail(DEKF_ERR_INVALID, "dekf_set_instance_params needs a direct MHE handle: this is a KF handle (est_type 1)");
-    if (h->pipelined) return fail(DEKF_ERR_INVALID, "dekf_set_instance_params cannot be combined with solve_pipeline = 1");
-    if (h->solver != DEKF_SOLVER_DIRECT) return fail(DEKF_ERR_INVALID, "dekf_set_instance_params needs a direct handle (dekf_set_solver(h, DEKF_SOLVER_DIRECT))");
+    TRY(need_direct(h, "dekf_set_instance_params", false));  // (allowed before dekf_initialize: that is when a fresh handle takes its table)
     if (nsets < 0) return fail(DEKF_ERR_INVALID, "dekf_set_instance_params: nsets must be >= 0");
     if (nsets == 0 ? (sets || set_of) : (!sets || !set_of))
         return fail(DEKF_ERR_INVALID, "dekf_set_instance_params: sets and set_of must both be given (nsets > 0) or both be NULL (nsets = 0)");
     const size_t B = (size_t)h->c.B;
+    dekf_handle_s::Instances& in = h->inst;
     const bool fresh = !h->initialized && h->ekf_count == 0;  // before the first tick since dekf_create / dekf_reset
     if (nsets == 0) {  // drop the table: the handle's own constants for every instance, and its former kernels
-        if (!h->pp) return DEKF_OK;
+        if (instance_mode(h).clock != Clock::PARAM) return DEKF_OK;
         if (!fresh) return fail(DEKF_ERR_ORDER, "dekf_set_instance_params: the table is dropped before the first tick or right after dekf_reset");
         HIPCHK(hipSetDevice(h->device));
         TRY(quiesce(h));
-        h->pp = false;
-        h->inst_prm.clear();
-        k_reset_state<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->s);  // (the EKF state at the handle's initial values)
+        in.table = false;
+        in.inst_prm.clear();
+        launch_reset_state(h, h->s);  // (no table any more: k_reset_state, the EKF state at the handle's initial values)
         HIPCHK(hipGetLastError());
         return DEKF_OK;
     }
@@ -1024,51 +1062,51 @@ dekf_status dekf_set_instance_params(dekf_handle h, const dekf_params* sets, int
             // only an instance that dekf_reset_instances has restarted and that has seen neither an update nor an EKF tick since:
             // its own local step is -1 and its own local EKF count 0, whatever the handle ticked before the restart (or ticks
             // while the instance is paused: mhe_pause_core.h)
-            const bool restarted = h->initialized && h->epochs &&
-                                   instance_tick((int)b, T, h->act_host.data(), h->pz_step.data(), h->t0_host.data()) == -1 &&
-                                   instance_count((int)b, h->ekf_count, h->act_host.data(), h->pz_count.data(), h->c0_host.data()) == 0;
+            const bool restarted = h->initialized && instance_mode(h).restarted &&
+                                   instance_tick((int)b, T, in.act_host.data(), in.pz_step.data(), in.t0_host.data()) == -1 &&
+                                   instance_count((int)b, h->ekf_count, in.act_host.data(), in.pz_count.data(), in.c0_host.data()) == 0;
             if (!restarted)
                 return fail(DEKF_ERR_ORDER, "dekf_set_instance_params: an instance takes a set before its first tick only (before the first "
                                             "dekf_ekf_step, right after dekf_reset, or right after dekf_reset_instances restarted it)");
         }
     HIPCHK(hipSetDevice(h->device));
     TRY(quiesce(h));  // (the arrival cost computed ahead reads the table)
-    TRY(ensure_epochs(h));
-    if (!h->pp_mhe) {
-        TRY(dev_alloc(h, B * sizeof(DevCfg), &h->pp_mhe));
-        TRY(dev_alloc(h, B * PpEkf::len * sizeof(double), &h->pp_ekf));
+    TRY(in.ensure(h));
+    if (!in.pp_mhe) {
+        TRY(dev_alloc(h, B * sizeof(DevCfg), &in.pp_mhe));
+        TRY(dev_alloc(h, B * PpEkf::len * sizeof(double), &in.pp_ekf));
     }
-    if (!h->pp) h->inst_prm.assign(B, h->prm);  // (a new table: every instance on the handle's own set)
+    if (instance_mode(h).clock != Clock::PARAM) in.inst_prm.assign(B, h->prm);  // (a new table: every instance on the handle's own set)
     for (size_t b = 0; b < B; ++b)
-        if (set_of[b] >= 0) h->inst_prm[b] = with_noise_of(h->prm, sets[set_of[b]]);
+        if (set_of[b] >= 0) in.inst_prm[b] = with_noise_of(h->prm, sets[set_of[b]]);
     // both tables are written whole from the host's copy (the entries of untouched instances with the values they hold): the handle's
     // DevCfg with the constants fill_cfg derives for a handle created with the instance's set
     std::vector<DevCfg> tm(B, h->c);
     std::vector<double> te(B * PpEkf::len);
     std::vector<int> mask(B);
     for (size_t b = 0; b < B; ++b) {
-        fill_noise(h->inst_prm[b], tm[b]);
+        fill_noise(in.inst_prm[b], tm[b]);
         pp_pack_ekf(tm[b], te.data(), B, b);
         mask[b] = set_of[b] >= 0;
     }
-    HIPCHK(hipMemcpyAsync(h->pp_mhe, tm.data(), tm.size() * sizeof(DevCfg), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->pp_ekf, te.data(), te.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(in.pp_mhe, tm.data(), tm.size() * sizeof(DevCfg), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(in.pp_ekf, te.data(), te.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (any) {  // the EKF state of the instances that took a set: their set's initial quaternion and covariance
         const int* dmask = mask.data();
         TRY(ensure_stage(h, B * sizeof(int)));
         TRY(stage_in(h, 0, &dmask, B));
-        k_ekf_init_pp<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->s, dmask, h->pp_ekf);
+        k_ekf_init_pp<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->s, dmask, in.pp_ekf);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(h->stream));  // (the sources of the copies are locals)
-    h->pp = true;
+    in.table = true;
     return DEKF_OK;
 }
 
 dekf_status dekf_get_instance_params(dekf_handle h, int b, dekf_params* out) {
     if (!h || !out) return fail(DEKF_ERR_INVALID, "null argument");
     if (b < 0 || b >= h->c.B) return fail(DEKF_ERR_INVALID, "dekf_get_instance_params: instance out of range");
-    *out = h->pp ? h->inst_prm[(size_t)b] : h->prm;
+    *out = instance_mode(h).clock == Clock::PARAM ? h->inst.inst_prm[(size_t)b] : h->prm;
     return DEKF_OK;
 }
 
@@ -1142,8 +1180,7 @@ dekf_status dekf_push_vo(dekf_handle h, const int* mask, const double* t_pre, co
             TRY(stage_in(h, 6 * B * 8, &q_vo, 4 * B));
         }
     }
-    if (h->pausing) k_latch_vo_act<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->s, mask, h->ep_t0, t_pre, t_now, dp_body, t_pose, q_vo);
-    else k_latch_vo<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->c, h->s, mask, t_pre, t_now, dp_body, t_pose, q_vo);
+    launch_latch_vo(h, mask, t_pre, t_now, dp_body, t_pose, q_vo);
     HIPCHK(hipGetLastError());
     return DEKF_OK;
 }
@@ -1155,14 +1192,7 @@ dekf_status dekf_push_quaternion(dekf_handle h, const double* quat, dekf_mem whe
 
 dekf_status dekf_ekf_step(dekf_handle h) {
     if (!h) return fail(DEKF_ERR_INVALID, "null handle");
-    {
-        Timed t(h, 0);
-        if (h->pausing && h->pp) k_ekf_tick_act_pp<<<(h->c.B + 63) / 64, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count, h->ep_c0, h->pp_ekf);
-        else if (h->pausing) k_ekf_tick_act<<<(h->c.B + 63) / 64, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count, h->ep_c0);
-        else if (h->pp) k_ekf_tick_pp<<<(h->c.B + 63) / 64, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count, h->ep_c0, h->pp_ekf);
-        else if (h->epochs) k_ekf_tick_ep<<<(h->c.B + 63) / 64, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count, h->ep_c0);
-        else k_ekf_tick<<<(h->c.B + 63) / 64, 64, 0, h->stream>>>(h->c, h->s, h->ekf_count);
-    }
+    { Timed t(h, 0); launch_tick(h); }
     HIPCHK(hipGetLastError());
     h->ekf_count++;
     // the kernel uses the count only modulo the ring depth and to know whether the ring is full: folded long before
@@ -1172,11 +1202,10 @@ dekf_status dekf_ekf_step(dekf_handle h) {
         // A restarted instance's tick runs on its local count, ekf_count - c0[b]: every epoch is moved so that the local count keeps
         // its value modulo the ring depth and whether it has reached it (mhe_epoch_core.h: fold_epoch).  An epoch of 0 stays 0.
         // A paused instance's epoch is the sentinel and stays it; its stored local count needs no fold (mhe_pause_core.h).
-        if (h->epochs) {
-            if (h->pausing) k_fold_epochs_act<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->ep_c0, h->c.B, h->ekf_count, folded, h->c.ekf_hist);
-            else k_fold_epochs<<<(h->c.B + 255) / 256, 256, 0, h->stream>>>(h->ep_c0, h->c.B, h->ekf_count, folded, h->c.ekf_hist);
+        if (instance_mode(h).restarted) {
+            launch_fold(h, h->ekf_count, folded);
             HIPCHK(hipGetLastError());
-            for (int& c0 : h->c0_host) c0 = fold_epoch_active(c0, h->ekf_count, folded, h->c.ekf_hist);  // (the host's copy moves alike)
+            for (int& c0 : h->inst.c0_host) c0 = fold_epoch_active(c0, h->ekf_count, folded, h->c.ekf_hist);  // (the host's copy moves alike)
         }
         h->ekf_count = folded;
     }
@@ -1187,8 +1216,7 @@ dekf_status dekf_initialize(dekf_handle h) {
     if (!h) return fail(DEKF_ERR_INVALID, "null handle");
     if (h->initialized) return fail(DEKF_ERR_ORDER, "dekf_initialize called twice without dekf_reset");
     if (h->c.est_type == 0) {
-        // (a handle with a parameter table: the epoch path, whose step 0 is the initialise path on every instance's own prior)
-        if (h->pp) k_mhe_assemble_pp<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->s, 0, 0, h->ep_t0, h->pp_mhe);
+        if (instance_mode(h).clock == Clock::PARAM) launch_assemble(h, h->s, 0, 0);  // (nobody is restarted or paused before this call)
         else k_mhe_initialize<<<h->c.B, 64, h->lds_asm, h->stream>>>(h->c, h->s);
         h->pushes = 1;
     } else {
@@ -1206,7 +1234,7 @@ dekf_status dekf_update(dekf_handle h, int T) {
     if (!h) return fail(DEKF_ERR_INVALID, "null handle");
     if (!h->initialized) return fail(DEKF_ERR_ORDER, "dekf_update before dekf_initialize");
     if (T != h->next_T) return fail(DEKF_ERR_ORDER, "update(T) must be called with T = 1, 2, 3, ... (EstSub.cpp:58-75)");
-    if (h->pausing && T >= DEKF_EPOCH_PAUSED) return fail(DEKF_ERR_ORDER, "a handle that has paused an instance runs 2^31 - 2^16 steps: dekf_reset it");
+    if (instance_mode(h).paused && T >= DEKF_EPOCH_PAUSED) return fail(DEKF_ERR_ORDER, "a handle that has paused an instance runs 2^31 - 2^16 steps: dekf_reset it");
     if (h->c.est_type == 0) {
         // the terms, the solve behind them (pipelined: on its own stream), in-order: the next step's arrival cost beside the solve
         const MheStep st = mhe_step(h, T);
@@ -1323,7 +1351,7 @@ dekf_status dekf_set_solver(dekf_handle h, int solver) {
     if (h->c.est_type != 0) return fail(DEKF_ERR_INVALID, "the solver is an MHE setting: this is a KF handle (est_type 1)");
     if (h->pipelined) return fail(DEKF_ERR_INVALID, "dekf_set_solver cannot be combined with solve_pipeline = 1");
     if (h->initialized) return fail(DEKF_ERR_ORDER, "dekf_set_solver is allowed before dekf_initialize or right after dekf_reset");
-    if (solver == DEKF_SOLVER_ADMM && h->pp)
+    if (solver == DEKF_SOLVER_ADMM && instance_mode(h).clock == Clock::PARAM)
         return fail(DEKF_ERR_INVALID, "the handle has a parameter table (dekf_set_instance_params): drop it first (nsets = 0)");
     if (solver == DEKF_SOLVER_DIRECT) {
         if (h->c.polish) return fail(DEKF_ERR_INVALID, "the direct solve cannot be combined with osqp.polish = 1");

@@ -6,7 +6,7 @@
 //                     workgroup owns one scratch slab in HBM, so a slab is only ever touched
 //                     from one XCD (its L2 is the only one that caches it)
 //                     (mhe_solve_core.h, mhe_admm_core.h)
-//   k_mhe_solve_direct_*  the direct solve (dekf_set_solver), one wavefront per instance (mhe_direct_core.h)
+//   k_mhe_solve_direct_*  the direct solve (dekf_set_solver), one wavefront per instance: rows x variants of direct_kernels.def (mhe_direct_core.h)
 //   k_mhe_innov_*     the innovation statistics behind the direct solve (dekf_set_innovation), one wavefront per instance (mhe_innov_core.h)
 //   k_kf_*            KF alternative                      (kf_core.h)
 //   k_latch_vo        masked VO latch (robotSub::vo_callback for a batch)
@@ -267,88 +267,26 @@ __global__ void __launch_bounds__(64, DEKF_ASM_WAVES) k_mhe_assemble_act_pp(DevS
 
 // The direct solve kernels (direct_kernels.def): one wavefront per instance, a grid of B; every instance does the same work, so the
 // instance queue of the ADMM kernels would gain nothing.  cov: Cov(x_T) per instance, [B][ns][ns].
-// Every row also defines its smoothing twin NAME_smooth (dekf_set_smoother): direct_solve_t's SMOOTH instantiation, the backward pass
-// in the same launch; win: the window stores (mhe_direct_core.h: DirectWindow).  NAME itself is the instantiation it was.
-// And the twin of that, NAME_smooth_cross (dekf_set_window_cross): the CROSS instantiation, whose backward pass also leaves the lag-one and
-// to-newest cross-covariances; cross: the store of the latter (DirectCross).  NAME and NAME_smooth are the instantiations they were.
-// And every one of the three has its epoch twin NAME_ep, NAME_smooth_ep, NAME_smooth_cross_ep, which a handle launches once
-// dekf_reset_instances has restarted an instance: it takes the handle's step T in place of (kstart, K), reads its instance's epoch
-// t0[blockIdx.x] (one scalar load per workgroup) and calls the instantiation its sibling calls on the instance's local window, or
-// nothing at the instance's local step 0 (mhe_epoch_core.h).  The three siblings are the code they were.
-// And every epoch twin has its parameter twin NAME_pp, NAME_smooth_pp, NAME_smooth_cross_pp, which a handle with a parameter table
-// launches (dekf_set_instance_params): the epoch twin on its instance's DevCfg of the table (pc[blockIdx.x], scalar loads from a
-// workgroup-uniform address) in place of the handle's in the kernel arguments (mhe_params_core.h).  Of the noise constants the direct
-// solve reads Q_bias_dt2 alone; the rest is in the window records the assemble step wrote.
-#define DEKF_DIRECT_EPOCH_TWINS_(NAME, L, FT)                                                                                 \
-    __global__ void __launch_bounds__(64) NAME##_ep(DevCfg c, DevState s, int T, double* cov, const int* t0) {               \
+// Every row of the catalogue is defined once per variant of its list, NAME##SUFFIX: direct_solve_t's <L, FT, SMOOTH, CROSS>
+// instantiation (win: the window stores, DirectWindow; cross: the store of the to-newest cross-covariances, DirectCross) inside the
+// body of the variant's clock.  EPOCH: one scalar load of the epoch per workgroup, then the instance's local window, or nothing at its
+// local step 0 (mhe_epoch_core.h).  PARAM: the same on pc[blockIdx.x] (scalar loads from a workgroup-uniform address, mhe_params_core.h);
+// of the noise constants the direct solve reads Q_bias_dt2 alone, the rest is in the window records the assemble step wrote.
+#define DEKF_DIRECT_BODY_WINDOW(...) __VA_ARGS__;
+#define DEKF_DIRECT_BODY_EPOCH(...) int kstart, K; if (direct_window_epoch(c, T, t0[blockIdx.x], kstart, K)) __VA_ARGS__;
+#define DEKF_DIRECT_BODY_PARAM(...) const DevCfg& c = pc[blockIdx.x]; DEKF_DIRECT_BODY_EPOCH(__VA_ARGS__)
+#define DEKF_DIRECT_DEFINE_(SUFFIX, SMOOTH, CROSS, CLOCK, NAME, L, FT)                                                        \
+    __global__ void __launch_bounds__(64) NAME##SUFFIX(DEKF_DIRECT_PARAMS(SMOOTH, CROSS, CLOCK)) {                            \
         extern __shared__ double lds[];                                                                                      \
-        int kstart, K;                                                                                                       \
-        if (direct_window_epoch(c, T, t0[blockIdx.x], kstart, K)) direct_solve_t<L, FT>(c, s, blockIdx.x, kstart, K, lds, cov); \
-    }                                                                                                                        \
-    __global__ void __launch_bounds__(64) NAME##_smooth_ep(DevCfg c, DevState s, int T, double* cov, DirectWindow win, const int* t0) { \
-        extern __shared__ double lds[];                                                                                      \
-        int kstart, K;                                                                                                       \
-        if (direct_window_epoch(c, T, t0[blockIdx.x], kstart, K))                                                            \
-            direct_solve_t<L, FT, true>(c, s, blockIdx.x, kstart, K, lds, cov, win);                                          \
-    }                                                                                                                        \
-    __global__ void __launch_bounds__(64) NAME##_smooth_cross_ep(DevCfg c, DevState s, int T, double* cov, DirectWindow win, \
-                                                                 DirectCross cross, const int* t0) {                         \
-        extern __shared__ double lds[];                                                                                      \
-        int kstart, K;                                                                                                       \
-        if (direct_window_epoch(c, T, t0[blockIdx.x], kstart, K))                                                            \
-            direct_solve_t<L, FT, true, true>(c, s, blockIdx.x, kstart, K, lds, cov, win, cross);                             \
-    }                                                                                                                        \
-    __global__ void __launch_bounds__(64) NAME##_pp(DevState s, int T, double* cov, const int* t0,                           \
-                                                    const DevCfg* __restrict__ pc) {                                         \
-        extern __shared__ double lds[];                                                                                      \
-        int kstart, K;                                                                                                       \
-        const DevCfg& c = pc[blockIdx.x];                                                                                    \
-        if (direct_window_epoch(c, T, t0[blockIdx.x], kstart, K)) direct_solve_t<L, FT>(c, s, blockIdx.x, kstart, K, lds, cov); \
-    }                                                                                                                        \
-    __global__ void __launch_bounds__(64) NAME##_smooth_pp(DevState s, int T, double* cov, DirectWindow win, const int* t0, \
-                                                           const DevCfg* __restrict__ pc) {                                  \
-        extern __shared__ double lds[];                                                                                      \
-        int kstart, K;                                                                                                       \
-        const DevCfg& c = pc[blockIdx.x];                                                                                    \
-        if (direct_window_epoch(c, T, t0[blockIdx.x], kstart, K))                                                            \
-            direct_solve_t<L, FT, true>(c, s, blockIdx.x, kstart, K, lds, cov, win);                                          \
-    }                                                                                                                        \
-    __global__ void __launch_bounds__(64) NAME##_smooth_cross_pp(DevState s, int T, double* cov, DirectWindow win,            \
-                                                                 DirectCross cross, const int* t0, const DevCfg* __restrict__ pc) { \
-        extern __shared__ double lds[];                                                                                      \
-        int kstart, K;                                                                                                       \
-        const DevCfg& c = pc[blockIdx.x];                                                                                    \
-        if (direct_window_epoch(c, T, t0[blockIdx.x], kstart, K))                                                            \
-            direct_solve_t<L, FT, true, true>(c, s, blockIdx.x, kstart, K, lds, cov, win, cross);                             \
+        DEKF_DIRECT_BODY_##CLOCK(direct_solve_t<L, FT, SMOOTH, CROSS>(c, s, blockIdx.x, kstart, K, lds, cov                   \
+                                                                      DEKF_DIRECT_IF_##SMOOTH(, win) DEKF_DIRECT_IF_##CROSS(, cross))) \
     }
-#define DEKF_DIRECT_KERNEL(NAME, L, FT, NFIX)                                                                                 \
-    __global__ void __launch_bounds__(64) NAME(DevCfg c, DevState s, int kstart, int K, double* cov) {                         \
-        extern __shared__ double lds[];                                                                                      \
-        direct_solve_t<L, FT>(c, s, blockIdx.x, kstart, K, lds, cov);                                                         \
-    }                                                                                                                        \
-    __global__ void __launch_bounds__(64) NAME##_smooth(DevCfg c, DevState s, int kstart, int K, double* cov, DirectWindow win) { \
-        extern __shared__ double lds[];                                                                                      \
-        direct_solve_t<L, FT, true>(c, s, blockIdx.x, kstart, K, lds, cov, win);                                              \
-    }                                                                                                                        \
-    __global__ void __launch_bounds__(64) NAME##_smooth_cross(DevCfg c, DevState s, int kstart, int K, double* cov, DirectWindow win, \
-                                                              DirectCross cross) {                                           \
-        extern __shared__ double lds[];                                                                                      \
-        direct_solve_t<L, FT, true, true>(c, s, blockIdx.x, kstart, K, lds, cov, win, cross);                                 \
-    }                                                                                                                        \
-    DEKF_DIRECT_EPOCH_TWINS_(NAME, L, FT)
+#define DEKF_DIRECT_STUB_(SUFFIX, SMOOTH, CROSS, CLOCK, NAME) __global__ void NAME##SUFFIX(DEKF_DIRECT_PARAMS(SMOOTH, CROSS, CLOCK)) {}
+#define DEKF_DIRECT_KERNEL(NAME, L, FT, NFIX) DEKF_DIRECT_VARIANTS(DEKF_DIRECT_DEFINE_, NAME, L, FT)
 #ifdef DEKF_KSET_ONLY
 #define DEKF_DIRECT_KERNEL_OFF(...)
 #else
-#define DEKF_DIRECT_KERNEL_OFF(NAME, ...)                               \
-    __global__ void NAME(DevCfg, DevState, int, int, double*) {}        \
-    __global__ void NAME##_smooth(DevCfg, DevState, int, int, double*, DirectWindow) {} \
-    __global__ void NAME##_smooth_cross(DevCfg, DevState, int, int, double*, DirectWindow, DirectCross) {} \
-    __global__ void NAME##_ep(DevCfg, DevState, int, double*, const int*) {} \
-    __global__ void NAME##_smooth_ep(DevCfg, DevState, int, double*, DirectWindow, const int*) {} \
-    __global__ void NAME##_smooth_cross_ep(DevCfg, DevState, int, double*, DirectWindow, DirectCross, const int*) {} \
-    __global__ void NAME##_pp(DevState, int, double*, const int*, const DevCfg*) {} \
-    __global__ void NAME##_smooth_pp(DevState, int, double*, DirectWindow, const int*, const DevCfg*) {} \
-    __global__ void NAME##_smooth_cross_pp(DevState, int, double*, DirectWindow, DirectCross, const int*, const DevCfg*) {}
+#define DEKF_DIRECT_KERNEL_OFF(NAME, ...) DEKF_DIRECT_VARIANTS(DEKF_DIRECT_STUB_, NAME)
 #endif
 #include "direct_kernels.def"
 
