@@ -62,6 +62,8 @@ PROTOTYPES = {
     "dekf_get_active": (C.c_int, [_vp, _vp, C.c_int]),
     "dekf_set_innovation": (C.c_int, [_vp, C.c_int]),
     "dekf_get_innovation": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int]),
+    "dekf_set_innovation_gate": (C.c_int, [_vp, C.c_double]),
+    "dekf_get_innovation_gate": (C.c_int, [_vp, _dp, _vp, C.c_int]),
     "dekf_timing_enable":(C.c_int, [_vp, C.c_int]),
     "dekf_timing_read": (C.c_int, [_vp, _dp, _ip]),
     "dekf_launch_info": (C.c_int, [_vp, _ip, _ip, _dp]),

@@ -14,6 +14,7 @@
 #include "mhe_assemble_core.h"
 #include "mhe_direct_core.h"
 #include "mhe_epoch_core.h"
+#include "mhe_gate_core.h"
 #include "mhe_innov_core.h"
 #include "mhe_params_core.h"
 #include "mhe_pause_core.h"
@@ -47,6 +48,16 @@ DEKF_INNOV_KERNEL(3)
 DEKF_INNOV_KERNEL(4)
 #undef DEKF_INNOV_KERNEL
 __global__ void k_innov_nan(DevCfg c, const int* mask, InnovStore out);
+// the gate kernels (mhe_gate_core.h): the innovation kernel's body with the gate behind it, one per leg count, and their epoch twins
+#define DEKF_GATE_KERNEL(L)                                                                                                       \
+    __global__ void k_mhe_innov_gate_##L(DevCfg c, DevState s, int kstart, int K, double* cov, InnovStore out, GateStore gs);     \
+    __global__ void k_mhe_innov_gate_##L##_ep(DevCfg c, DevState s, int T, double* cov, InnovStore out, GateStore gs, const int* t0, \
+                                              const DevCfg* pc);
+DEKF_GATE_KERNEL(1)
+DEKF_GATE_KERNEL(2)
+DEKF_GATE_KERNEL(3)
+DEKF_GATE_KERNEL(4)
+#undef DEKF_GATE_KERNEL
 __global__ void k_gap();
 __global__ void k_kf_initialize(DevCfg c, DevState s);
 __global__ void k_kf_update(DevCfg c, DevState s, int pushes);
@@ -132,6 +143,10 @@ struct dekf_handle_s {
     bool innov = false;
     InnovStore innov_st;
     bool innov_valid = false;
+    // dekf_set_innovation_gate: a gating handle (gate_st.nis_leg_max > 0; an innovation handle) launches the gate kernel of its leg
+    // count (mhe_gate_core.h) in place of the innovation kernel.  gate_st.gated: [B][L] ints, allocated by the first call that
+    // switches the gate on, zeroed by dekf_reset and, for the restarted instances, by dekf_reset_instances
+    GateStore gate_st;
     // The per-instance state of a direct handle: what dekf_reset_instances, dekf_set_active and dekf_set_instance_params keep.
     struct Instances {
         // dekf_reset_instances: the epochs (mhe_epoch_core.h).  t0 | c0: [B] ints each on the device (one block), the handle's step
@@ -308,6 +323,12 @@ typedef void (*InnovEpochFn)(DevCfg, DevState, int, const double*, InnovStore, c
 struct InnovKernel { InnovFn fn; InnovEpochFn fn_ep; };
 const InnovKernel innov_kernels[DEKF_MAX_LEGS] = {{k_mhe_innov_1, k_mhe_innov_1_ep}, {k_mhe_innov_2, k_mhe_innov_2_ep},
                                                   {k_mhe_innov_3, k_mhe_innov_3_ep}, {k_mhe_innov_4, k_mhe_innov_4_ep}};
+// The gate kernels as dekf_set_innovation_gate selects them, in the same way
+typedef void (*GateFn)(DevCfg, DevState, int, int, double*, InnovStore, GateStore);
+typedef void (*GateEpochFn)(DevCfg, DevState, int, double*, InnovStore, GateStore, const int*, const DevCfg*);
+struct GateKernel { GateFn fn; GateEpochFn fn_ep; };
+const GateKernel gate_kernels[DEKF_MAX_LEGS] = {{k_mhe_innov_gate_1, k_mhe_innov_gate_1_ep}, {k_mhe_innov_gate_2, k_mhe_innov_gate_2_ep},
+                                                {k_mhe_innov_gate_3, k_mhe_innov_gate_3_ep}, {k_mhe_innov_gate_4, k_mhe_innov_gate_4_ep}};
 
 // the kernel of its row that a direct handle launches: the variant of the list with the handle's smoother and cross settings and the
 // clock of its instance mode
@@ -332,17 +353,22 @@ struct SolveLaunch {
     // lds_innov of LDS
     const InnovKernel* innov;
     size_t lds_innov;
+    // ... or, on a gating handle (dekf_set_innovation_gate), the gate kernel of its leg count IN PLACE of the innovation kernel (null:
+    // none; `innov` is then null): the same grid, lds_innov of LDS.  The epoch twin takes the parameter table, or null
+    const GateKernel* gate;
 };
 SolveLaunch solve_launch(const dekf_handle_s* h, int K) {
     if (h->solver == DEKF_SOLVER_DIRECT) {
         const DirectVariant v = direct_variant(h);
-        return {h->direct->name[v], h->c.B, 64, h->lds_direct, nullptr, v, h->innov ? &innov_kernels[h->c.L - 1] : nullptr,
-                (size_t)InnovScratch::len(h->c.L) * sizeof(double)};
+        const bool gate = h->innov && h->gate_st.nis_leg_max > 0.0;
+        return {h->direct->name[v], h->c.B, 64, h->lds_direct, nullptr, v, h->innov && !gate ? &innov_kernels[h->c.L - 1] : nullptr,
+                (size_t)(gate ? GateScratch::len(h->c.L) : InnovScratch::len(h->c.L)) * sizeof(double),
+                gate ? &gate_kernels[h->c.L - 1] : nullptr};
     }
     const bool full = h->solve_entry_full && K == h->c.N;
     const SolveTwin t = solve_twin(full ? h->solve_entry_full : h->solve_entry, h->c.polish != 0, h->c.warm != 0);
-    if (full) return {t.name, h->solve_grid_full, h->solve_threads_full, h->lds_solve_full, t.fn, dv_count, nullptr, 0};
-    return {t.name, h->solve_grid, DEKF_SOLVE_THREADS, h->lds_solve, t.fn, dv_count, nullptr, 0};
+    if (full) return {t.name, h->solve_grid_full, h->solve_threads_full, h->lds_solve_full, t.fn, dv_count, nullptr, 0, nullptr};
+    return {t.name, h->solve_grid, DEKF_SOLVE_THREADS, h->lds_solve, t.fn, dv_count, nullptr, 0, nullptr};
 }
 
 // A family of full-window kernels (K == N): the shapes it covers are the rows of its role in solve_kernels.def
@@ -543,6 +569,14 @@ void launch_solve(dekf_handle h, const SolveLaunch& l, const DevState& sp, int T
     switch (l.variant) {
     DEKF_DIRECT_VARIANTS(DEKF_DIRECT_LAUNCH_)
     case dv_count: break;
+    }
+    if (l.gate) {  // (a gating handle: the statistics, then the gate on them, in one launch)
+        if (direct_variants[l.variant].clock == Clock::WINDOW)
+            l.gate->fn<<<l.grid, 64, l.lds_innov, ss>>>(h->c, sp, kstart, K, h->mhe_cov, h->innov_st, h->gate_st);
+        else
+            l.gate->fn_ep<<<l.grid, 64, l.lds_innov, ss>>>(h->c, sp, T, h->mhe_cov, h->innov_st, h->gate_st, h->inst.t0,
+                                                           direct_variants[l.variant].clock == Clock::PARAM ? h->inst.pp_mhe : nullptr);
+        return;
     }
     if (!l.innov) return;
     // (an innovation handle: the statistics of the newest step from what the solve just left, in stream order behind it)
@@ -948,6 +982,7 @@ dekf_status dekf_reset(dekf_handle h) {
     h->innov_valid = false;
     if (h->innov_st.nu)  // every entry NaN again (all bits set is one): an instance keeps it until its first solve
         HIPCHK(hipMemsetAsync(h->innov_st.nu, 0xff, (size_t)h->c.B * InnovStore::len(h->c.L) * sizeof(double), h->stream));
+    if (h->gate_st.gated) HIPCHK(hipMemsetAsync(h->gate_st.gated, 0, (size_t)h->c.B * h->c.L * sizeof(int), h->stream));  // (the bound survives)
     h->win_steps = 0;
     TRY(h->inst.clear(h));
     return DEKF_OK;
@@ -974,6 +1009,13 @@ dekf_status dekf_reset_instances(dekf_handle h, const int* mask, dekf_mem where)
     }
     launch_reset_instances(h, dmask);
     HIPCHK(hipGetLastError());
+    if (h->gate_st.gated)  // the restarted instances have gated nothing: their entries 0, one fill per run of them
+        for (size_t b = 0; b < B;) {
+            size_t e = b;
+            while (e < B && m[e] == 1) ++e;
+            if (e > b) HIPCHK(hipMemsetAsync(h->gate_st.gated + b * h->c.L, 0, (e - b) * h->c.L * sizeof(int), h->stream));
+            b = e > b ? e : b + 1;
+        }
     if (where == DEKF_HOST) HIPCHK(hipStreamSynchronize(h->stream));  // (m, a local, is the source of the copy)
     for (size_t b = 0; b < B; ++b)  // (a paused instance that is restarted is active: its new life starts here)
         if (m[b]) restart_instance((int)b, in.act_host.data(), in.t0_host.data(), in.c0_host.data(), h->next_T, h->ekf_count);
@@ -1365,7 +1407,10 @@ dekf_status dekf_set_solver(dekf_handle h, int solver) {
     }
     h->solver = solver;
     h->mhe_cov_valid = false;
-    if (solver == DEKF_SOLVER_ADMM) h->smoother = h->cross = h->innov = false;  // the smoother, its cross-covariances and the innovation statistics are the direct solve's
+    if (solver == DEKF_SOLVER_ADMM) {  // the smoother, its cross-covariances, the innovation statistics and their gate are the direct solve's
+        h->smoother = h->cross = h->innov = false;
+        h->gate_st.nis_leg_max = 0.0;
+    }
     h->innov_valid = false;
     h->win_steps = 0;
     return DEKF_OK;
@@ -1374,6 +1419,8 @@ dekf_status dekf_set_solver(dekf_handle h, int solver) {
 dekf_status dekf_set_smoother(dekf_handle h, int on) {
     if (!h) return fail(DEKF_ERR_INVALID, "null handle");
     if (on != 0 && on != 1) return fail(DEKF_ERR_INVALID, "dekf_set_smoother: on must be 0 or 1");
+    if (on && h->gate_st.nis_leg_max > 0.0)
+        return fail(DEKF_ERR_INVALID, "the window smoother cannot be combined with the innovation gate (dekf_set_innovation_gate)");
     if (on && h->solver != DEKF_SOLVER_DIRECT) return fail(DEKF_ERR_INVALID, "the window smoother needs a direct handle (dekf_set_solver(h, DEKF_SOLVER_DIRECT))");
     if (h->initialized) return fail(DEKF_ERR_ORDER, "dekf_set_smoother is allowed before dekf_initialize or right after dekf_reset");
     if (on && !h->win.x) {
@@ -1448,7 +1495,34 @@ dekf_status dekf_set_innovation(dekf_handle h, int on) {
     }
     h->innov = on != 0;
     h->innov_valid = false;
+    if (!on) h->gate_st.nis_leg_max = 0.0;  // the gate is the statistics': switched off with them
     return DEKF_OK;
+}
+
+dekf_status dekf_set_innovation_gate(dekf_handle h, double nis_leg_max) {
+    if (!h) return fail(DEKF_ERR_INVALID, "null handle");
+    if (!(nis_leg_max >= 0.0) || !(nis_leg_max <= 1.7976931348623157e308))
+        return fail(DEKF_ERR_INVALID, "dekf_set_innovation_gate: nis_leg_max must be finite and not negative (0 switches the gate off)");
+    if (nis_leg_max > 0.0 && !h->innov) return fail(DEKF_ERR_INVALID, "the innovation gate needs an innovation handle (dekf_set_innovation(h, 1))");
+    if (nis_leg_max > 0.0 && h->smoother) return fail(DEKF_ERR_INVALID, "the innovation gate cannot be combined with the window smoother (dekf_set_smoother)");
+    if (h->initialized) return fail(DEKF_ERR_ORDER, "dekf_set_innovation_gate is allowed before dekf_initialize or right after dekf_reset");
+    if (nis_leg_max > 0.0 && !h->gate_st.gated) {
+        HIPCHK(hipSetDevice(h->device));
+        const size_t n = (size_t)h->c.B * h->c.L * sizeof(int);
+        TRY(dev_alloc(h, n, &h->gate_st.gated));
+        HIPCHK(hipMemsetAsync(h->gate_st.gated, 0, n, h->stream));
+    }
+    h->gate_st.nis_leg_max = nis_leg_max;
+    return DEKF_OK;
+}
+
+dekf_status dekf_get_innovation_gate(dekf_handle h, double* nis_leg_max, int* gated, dekf_mem where) {
+    if (!h) return fail(DEKF_ERR_INVALID, "null handle");
+    if (nis_leg_max) *nis_leg_max = h->gate_st.nis_leg_max;
+    if (!gated) return DEKF_OK;
+    if (!(h->gate_st.nis_leg_max > 0.0)) return fail(DEKF_ERR_INVALID, "dekf_get_innovation_gate: gated needs a gating handle (dekf_set_innovation_gate)");
+    TRY(fetch(h, gated, h->gate_st.gated, (size_t)h->c.B * h->c.L * sizeof(int), where));
+    return host_sync(h, where);
 }
 
 dekf_status dekf_get_innovation(dekf_handle h, double* innov, double* innov_cov, double* nis, double* nis_leg, double* loglik, dekf_mem where) {

@@ -24,6 +24,7 @@
 #include "mhe_direct_core.h"
 #include "mhe_epoch_core.h"
 #include "mhe_innov_core.h"
+#include "mhe_gate_core.h"
 #include "mhe_params_core.h"
 #include "mhe_pause_core.h"
 #include "mhe_solve_core.h"
@@ -129,6 +130,12 @@ extern "C" {
 #define DEKF_INNOV_KERNELS 1
 #else
 #define DEKF_INNOV_KERNELS 0
+#endif
+// ... and the gate kernels (dekf_set_innovation_gate) only with bit 4096: one more unit, one more remarks file
+#if !defined(DEKF_KSET_ONLY) || (defined(DEKF_KSET) && (DEKF_KSET & 4096))
+#define DEKF_GATE_KERNELS 1
+#else
+#define DEKF_GATE_KERNELS 0
 #endif
 #if DEKF_MISC_KERNELS
 __global__ void __launch_bounds__(64) k_ekf_tick(DevCfg c, DevState s, int count) {
@@ -329,6 +336,38 @@ __global__ void k_innov_nan(DevCfg c, const int* mask, InnovStore out) {
     out.loglik[b] = NAN;
 }
 #endif  // DEKF_INNOV_KERNELS
+
+#if DEKF_GATE_KERNELS
+// The gate kernels (dekf_set_innovation_gate, mhe_gate_core.h): what a gating handle launches IN PLACE of the innovation kernel of its
+// leg count, so there is no third launch.  The body of k_mhe_innov_L[_ep] with innovation_t called as it is there (the five arrays are
+// that kernel's bits), then gate_t in the same wavefront: the decision from the per-leg NIS, the edit of the newest record's Q_m block
+// and the rank-3 correction of x_mhe, v_b and cov[b].  A set of their own (bit 4096), carried by every build without -DDEKF_KSET_ONLY.
+// The epoch twin takes the parameter table too (pc, null on a handle without one): the swing gain written into the record is the
+// instance's own.
+#define DEKF_GATE_KERNEL(L)                                                                                                   \
+    __global__ void __launch_bounds__(64) k_mhe_innov_gate_##L(DevCfg c, DevState s, int kstart, int K, double* cov, InnovStore out, \
+                                                               GateStore gs) {                                               \
+        extern __shared__ double lds[];                                                                                      \
+        const int slot = (kstart + K - 1) % c.wcap;                                                                          \
+        const bool solved = innovation_t<L>(c, s, blockIdx.x, slot, cov, out, lds);                                          \
+        gate_t<L>(c, c, s, blockIdx.x, slot, cov, out, gs, solved, lds);                                                     \
+    }                                                                                                                        \
+    __global__ void __launch_bounds__(64) k_mhe_innov_gate_##L##_ep(DevCfg c, DevState s, int T, double* cov, InnovStore out, \
+                                                                    GateStore gs, const int* t0, const DevCfg* __restrict__ pc) { \
+        extern __shared__ double lds[];                                                                                      \
+        int kstart, K;                                                                                                       \
+        if (direct_window_epoch(c, T, t0[blockIdx.x], kstart, K)) {                                                          \
+            const int slot = (kstart + K - 1) % c.wcap;                                                                      \
+            const bool solved = innovation_t<L>(c, s, blockIdx.x, slot, cov, out, lds);                                      \
+            gate_t<L>(c, pc ? pc[blockIdx.x] : c, s, blockIdx.x, slot, cov, out, gs, solved, lds);                           \
+        }                                                                                                                    \
+    }
+DEKF_GATE_KERNEL(1)
+DEKF_GATE_KERNEL(2)
+DEKF_GATE_KERNEL(3)
+DEKF_GATE_KERNEL(4)
+#undef DEKF_GATE_KERNEL
+#endif  // DEKF_GATE_KERNELS
 
 #if DEKF_MISC_KERNELS
 __global__ void k_gap() {}

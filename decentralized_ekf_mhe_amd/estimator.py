@@ -57,7 +57,7 @@ def relative_cov(cov_win, cov_newest, k):
 
 class BatchedEstimator:
     def __init__(self, params: DekfParams, batch: int, device: int = 0, stream=None, warm_start: bool = False, solver: str = "admm",
-                 smoother: bool = False, cross: bool = False, innovation: bool = False):
+                 smoother: bool = False, cross: bool = False, innovation: bool = False, innovation_gate: float = 0.0):
         """warm_start: full-window solves start from the previous tick's shifted solution (dekf_set_warm_start; off by default).
         solver: "admm" (default, the reference's OSQP-style ADMM) or "direct" (the exact optimum of the window QP and its covariance,
         dekf_set_solver; see mhe_cov)
@@ -65,7 +65,9 @@ class BatchedEstimator:
         cross: a smoothing handle also leaves the window's lag-one and to-newest cross-covariances (dekf_set_window_cross; see
         window_cross).  It implies nothing else: without smoother=True the library refuses it
         innovation: a direct handle also leaves the innovation of the newest leg measurement, its covariance, the NIS (whole and per
-        leg) and the predictive log-likelihood of every tick (dekf_set_innovation; see innovation)"""
+        leg) and the predictive log-likelihood of every tick (dekf_set_innovation; see innovation)
+        innovation_gate: an innovation handle takes a stance leg whose per-leg NIS exceeds this bound out of the solve, as if it had been
+        in swing at that tick (dekf_set_innovation_gate; see innovation_gate).  0.0: off.  Without innovation=True the library refuses it"""
         if solver not in ("admm", "direct"):
             raise ValueError(f"solver must be 'admm' or 'direct', not {solver!r}")
         _torch_runtime_first()
@@ -86,6 +88,8 @@ class BatchedEstimator:
                 capi.check(self.lib.dekf_set_window_cross(self.h, 1))
             if innovation:
                 capi.check(self.lib.dekf_set_innovation(self.h, 1))
+            if innovation_gate != 0.0:
+                capi.check(self.lib.dekf_set_innovation_gate(self.h, float(innovation_gate)))
             if warm_start:
                 capi.check(self.lib.dekf_set_warm_start(self.h, 1))
         except capi.DekfError:
@@ -284,6 +288,14 @@ class BatchedEstimator:
         capi.check(self.lib.dekf_get_innovation(self.h, *[C.c_void_p(out[k].ctypes.data) for k in ("innov", "innov_cov", "nis", "nis_leg", "loglik")],
                                                 capi.DEKF_HOST))
         return out
+
+    def innovation_gate(self):
+        """(nis_leg_max, gated [B, L]) of a gating handle (dekf_get_innovation_gate): the bound, and 1 for the legs the last update took
+        out of the solve because their nis_leg exceeded it"""
+        gated = np.zeros((self.batch, self.params.num_legs), dtype=np.int32)
+        bound = C.c_double(0.0)
+        capi.check(self.lib.dekf_get_innovation_gate(self.h, C.byref(bound), C.c_void_p(gated.ctypes.data), capi.DEKF_HOST))
+        return bound.value, gated
 
     def kf_cov(self):
         ns = self.params.dim_state

@@ -506,6 +506,47 @@ dekf_status dekf_set_innovation(dekf_handle h, int on);
 dekf_status dekf_get_innovation(dekf_handle h, double* innov, double* innov_cov, double* nis, double* nis_leg, double* loglik,
                                 dekf_mem where);
 
+/* ---- innovation gate (opt-in, innovation handles): take a slipping stance leg out of the solve it has just entered ----------
+ * Two more additive symbols: DEKF_ABI_VERSION and dekf_params are unchanged, and a caller that never calls them launches exactly the
+ * kernels of before and gets the same bits.  nis_leg against a bound says that a stance foot slips; by then the direct solve has folded
+ * the leg's velocity rows into x_mhe, v_b and Cov(x_T) at the stance weight, and the window record keeps that weight for the next N
+ * windows and then the arrival cost.  With the gate the library acts on the number, on the device, in the launch that computed it.
+ * dekf_set_innovation_gate(h, nis_leg_max): 0 (default) switches the gate off, a positive value is the bound.  There is no default
+ * bound: INTEGRATION.md says how to choose one.  Call order as for dekf_set_smoother: before dekf_initialize or right after dekf_reset
+ * (else DEKF_ERR_ORDER); the setting survives dekf_reset.  DEKF_ERR_INVALID for a null handle; a value that is negative, NaN or
+ * infinite; a positive value on a handle without dekf_set_innovation(h, 1) (which excludes ADMM handles, KF handles and leg_odom_type 1);
+ * a positive value on a smoothing handle.  dekf_set_smoother(h, 1) on a gating handle is DEKF_ERR_INVALID too: at a gated tick the
+ * backward pass has already run on the ungated block, and x_win[K-1] == x_mhe is promised to the bit; the window of a gating handle is
+ * not part of this interface.  dekf_set_innovation(h, 0) and dekf_set_solver(h, DEKF_SOLVER_ADMM) switch the gate off; switching those
+ * back on does not switch it on again.  The first enable allocates B * num_legs ints.
+ * A gating handle's update launches k_mhe_innov_gate_<L> (or its epoch twin k_mhe_innov_gate_<L>_ep) IN PLACE of k_mhe_innov_<L>[_ep]:
+ * the same statistics, then the gate, in one launch; timing class 2 brackets it with the direct solve as before.
+ * The rule, per instance and update that solved: leg l is gated iff nis_leg[b][l] > nis_leg_max.  NaN compares false, so an instance
+ * whose solve or innovation failed gates nothing; a leg in swing never passes (its NIS is about 1e-14).  In leg_odom_type 0 a leg's
+ * contact flag changes exactly one thing in the window problem, the leg's 3 x 3 block of the Meas slack cost Q_m (diag of the swing
+ * gain, 1 / foot_swing_std^2, for contact 0).  Gating a leg means "this leg was in swing at this tick":
+ *  - the leg's block of the newest window record becomes that swing block, word for word what a contact flag of 0 would have written;
+ *    on a handle with a parameter table it is the instance's own foot_swing_std.  Every later window and the arrival cost see it;
+ *  - x_mhe, v_b and the instance's block of dekf_get_mhe_cov become the optimum and Cov(x_T) of the window QP with those blocks, by a
+ *    rank-3 correction of the posterior (every leg reads the same three velocity states), no second elimination;
+ *  - if a pivot of the correction is not positive and finite, or its result is not finite: the record edit stands, the instance's
+ *    status becomes DEKF_SOLVE_NUMERIC, x_mhe, v_b and its covariance block are NaN.  The next update solves from the records;
+ *  - the five arrays of dekf_get_innovation keep their values: they are those of the ungated problem, the evidence for the decision;
+ *  - gated[b][l] = 1 for the legs this update gated, 0 for the others.
+ * In bits: a bound so high that it never fires leaves every output equal to the same handle with the gate off.  At every update at
+ * which an instance gates nothing, dekf_get, dekf_get_mhe_cov, solver info and the five arrays are bit-identical to those of an
+ * innovation handle without the gate that is fed the same log with contact = 0 at every (tick, leg) this instance gated before.  At an
+ * update at which it gates, x_mhe, v_b and the covariance agree with that handle to rounding (not to the bit).  A robot's results do
+ * not depend on the batch it runs in.
+ * dekf_reset zeroes all of gated; dekf_reset_instances zeroes the restarted instances' entries, and from its restart on such an
+ * instance gives the bits of a fresh gating handle; a paused instance (dekf_set_active) keeps its gated as it keeps everything else.
+ * dekf_get_innovation_gate: *nis_leg_max (host memory, on any handle; 0 = off) and gated[B][num_legs] (ints; all 0 before the first
+ * update).  Either pointer may be NULL.  gated on a handle whose gate is off: DEKF_ERR_INVALID.  Host pointer: copy and synchronise;
+ * device pointer: in stream order, like dekf_get_mhe_cov.
+ * Not part of this interface: a bound per instance; a history of decisions (gated is the last update's); smoothing handles. */
+dekf_status dekf_set_innovation_gate(dekf_handle h, double nis_leg_max);
+dekf_status dekf_get_innovation_gate(dekf_handle h, double* nis_leg_max, int* gated, dekf_mem where);
+
 /* status[B] values written by dekf_update */
 #define DEKF_SOLVE_NONE 0       /* no solve yet (T = 0) */
 #define DEKF_SOLVE_OK 1         /* OSQP_SOLVED */

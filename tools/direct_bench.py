@@ -17,6 +17,10 @@ alternate inside one process, so that a drift of the machine does not land on on
     python tools/direct_bench.py --modes direct,direct_smooth,direct_cross --repeat 3   # the cross-covariances against theirs
     python tools/direct_bench.py go1 cassie pogox --modes direct,direct_innov --repeat 3   # the innovation statistics (dekf_set_innovation;
                                                      # profiles/r10_innovation_bench.jsonl; not for go1_foot: outside the interface)
+    python tools/direct_bench.py go1 cassie pogox --modes direct,direct_innov,direct_innov_gate --repeat 3   # the innovation gate
+                                                     # (dekf_set_innovation_gate; profiles/r11_gate_bench.jsonl).  The log then carries a
+                                                     # few foot slips (every 512th robot, three ticks) and the bound is high, so the
+                                                     # common path is "decide, gate nothing"; gated_last: legs gated at the last step
 --epoch measures what dekf_reset_instances costs the instances it does not restart: per mode ONE handle runs the unchanged direct
 kernel (`before`), then restarts instance 0, lets its window refill and runs the epoch twins (`after`); dekf_reset brings the handle
 back, and the two alternate --repeat times in one process.  One JSON line per shape (--out: profiles/r11_epoch_bench.jsonl).
@@ -54,7 +58,20 @@ SHAPES = {
 }
 MODES = {"cold": dict(), "warm": dict(warm_start=True), "direct": dict(solver="direct"),
          "direct_smooth": dict(solver="direct", smoother=True), "direct_cross": dict(solver="direct", smoother=True, cross=True),
-         "direct_innov": dict(solver="direct", innovation=True)}
+         "direct_innov": dict(solver="direct", innovation=True),
+         "direct_innov_gate": dict(solver="direct", innovation=True, innovation_gate=1e4)}
+GATE_SLIP = (-12.8, 8.0, -5.4)   # m/s, IMU frame: far above the bound on every shape (nis_leg of 4e4 and more)
+
+
+def add_slips(s, W, steps):
+    """foot slips on the first stance leg of every 512th robot at three ticks of the timed steps, the last step among them"""
+    import numpy as np
+    for k in (W + steps // 3, W + 2 * steps // 3, W + steps - 1):
+        for b in range(0, s["contact"].shape[1], 512):
+            legs = np.nonzero(s["contact"][k, b])[0]
+            if len(legs):
+                s["qdot"][k, b, legs[0]] += np.linalg.pinv(s["J"][k, b, legs[0]]) @ np.array(GATE_SLIP)
+    return s
 
 
 def one(p, B, sd, W, steps, mode):
@@ -85,11 +102,12 @@ def one(p, B, sd, W, steps, mode):
     tim = est2.timing_read()
     solved = float((est2.get()["status"] == 1).mean())
     kernel = est.solve_kernel_name(True)
+    gated = {"gated_last": int(est2.innovation_gate()[1].sum())} if mode == "direct_innov_gate" else {}
     est.close()
     est2.close()
     return {"steps_per_s": B * steps / dt, "solve_ms": tim["solve"][0] / max(tim["solve"][1], 1),
             "assemble_ms": tim["assemble"][0] / max(tim["assemble"][1], 1), "ekf_ms": tim["ekf"][0] / max(tim["ekf"][1], 1),
-            "solved_fraction": solved, "kernel": kernel}
+            "solved_fraction": solved, "kernel": kernel, **gated}
 
 
 def timed(est, sd, k0, steps, B):
@@ -283,7 +301,8 @@ def main():
     if a.out is None and a.epoch:
         a.out = os.path.join(ROOT, "profiles", "r11_epoch_bench.jsonl")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "r10_innovation_bench.jsonl" if "direct_innov" in modes else
+        a.out = os.path.join(ROOT, "profiles", "r11_gate_bench.jsonl" if "direct_innov_gate" in modes else
+                             "r10_innovation_bench.jsonl" if "direct_innov" in modes else
                              "r10_cross_bench.jsonl" if "direct_cross" in modes else
                              "r09_smoother_bench.jsonl" if "direct_smooth" in modes else "r08_direct_bench.jsonl")
     for name in a.shapes:
@@ -323,7 +342,10 @@ def main():
             torch.cuda.empty_cache()
             continue
         W = max(p.N + 10, 64)  # (as tools/bench_shapes.py: past the window fill and the first vision intervals)
-        sd = streams_to_device(make_streams(p, B, W + a.steps))
+        s = make_streams(p, B, W + a.steps)
+        if "direct_innov_gate" in modes:  # (every mode of the line runs the same log)
+            s = add_slips(s, W, a.steps)
+        sd = streams_to_device(s)
         line = {"shape": name, "batch": B, "N": int(p.N), "steps": a.steps}
         runs = {mode: [] for mode in modes}
         for _ in range(a.repeat):
@@ -344,6 +366,11 @@ def main():
         if "direct" in line and "direct_innov" in line:  # (timing class 2 brackets the solve and the innovation kernel as one launch)
             line["innov_solve_ms_over_direct"] = line["direct_innov"]["solve_ms"] / line["direct"]["solve_ms"]
             line["innov_steps_per_s_over_direct"] = line["direct_innov"]["steps_per_s"] / line["direct"]["steps_per_s"]
+        if "direct_innov_gate" in line:
+            for m, tag in (("direct", "direct"), ("direct_innov", "innov")):
+                if m in line:
+                    line[f"gate_solve_ms_over_{tag}"] = line["direct_innov_gate"]["solve_ms"] / line[m]["solve_ms"]
+                    line[f"gate_steps_per_s_over_{tag}"] = line["direct_innov_gate"]["steps_per_s"] / line[m]["steps_per_s"]
         if "direct_cross" in line:
             for m, tag in (("direct", "direct"), ("direct_smooth", "smooth")):
                 if m in line:
