@@ -18,6 +18,7 @@
 #include "mhe_innov_core.h"
 #include "mhe_params_core.h"
 #include "mhe_pause_core.h"
+#include "mhe_snapshot_core.h"
 #include "mhe_solve_core.h"
 
 using namespace dekf;
@@ -85,6 +86,9 @@ __global__ void k_mhe_assemble_act_pp(DevState s, int T, int pushes, const int* 
 __global__ void k_latch_vo_act(DevCfg c, DevState s, const int* mask, const int* t0, const double* t_pre, const double* t_now,
                                const double* dp, const double* t_pose, const double* q_vo);
 __global__ void k_fold_epochs_act(int* c0, int B, int count_old, int count_new, int H);
+// snapshots of single instances (mhe_snapshot_core.h)
+__global__ void k_save_instances(StateMap m, const int* idx, const SnapBooks* books, unsigned char* recs, size_t rec_bytes);
+__global__ void k_load_instances(StateMap m, const int* idx, const unsigned char* recs, size_t rec_bytes);
 __global__ void k_ekf_cov_out(DevCfg c, DevState s, double* out);
 __global__ void k_latch4(LatchCopy4 a);
 __global__ void k_go1_leg_odometry(DevCfg c, DevState s, const double* jp, const double* jv, const double* force,
@@ -147,6 +151,9 @@ struct dekf_handle_s {
     // count (mhe_gate_core.h) in place of the innovation kernel.  gate_st.gated: [B][L] ints, allocated by the first call that
     // switches the gate on, zeroed by dekf_reset and, for the restarted instances, by dekf_reset_instances
     GateStore gate_st;
+    // dekf_save_instances, dekf_load_instances: the state map (mhe_snapshot_core.h), every persistent per-instance array of `s`
+    // (host_common.h: state_map, at dekf_create) and the stores above, each appended where it is allocated
+    StateMap snap_map;
     // The per-instance state of a direct handle: what dekf_reset_instances, dekf_set_active and dekf_set_instance_params keep.
     struct Instances {
         // dekf_reset_instances: the epochs (mhe_epoch_core.h).  t0 | c0: [B] ints each on the device (one block), the handle's step
@@ -638,6 +645,14 @@ void launch_reset_instances(dekf_handle h, const int* dmask) {
     if (h->innov_st.nu) k_innov_nan<<<grid, 256, 0, h->stream>>>(h->c, dmask, h->innov_st);
 }
 
+// *steps of the window getters on a handle with epochs, behind the update of step T: the largest window of the batch, which is that of
+// the instance restarted (or loaded with the oldest record) longest ago, none at its local step 0, or of a paused one where it stands
+int epoch_window_steps(const dekf_handle_s* h, int T) {
+    const int Ta = T - h->inst.min_t0;
+    const int Tl = Ta > h->inst.max_frozen ? Ta : h->inst.max_frozen;
+    return Tl < 1 ? 0 : (Tl + 1 < h->c.N ? Tl + 1 : h->c.N);
+}
+
 // the terms of step T: waits for the snapshot copy to be free and for the arrival cost computed ahead, then the assemble
 dekf_status assemble_step(dekf_handle h, const MheStep& st) {
     if (h->pipelined && h->snap_busy[st.snap_set]) HIPCHK(hipStreamWaitEvent(h->stream, h->ev_snap_free[st.snap_set], 0));
@@ -683,11 +698,7 @@ dekf_status solve_step(dekf_handle h, const MheStep& st) {
     h->mhe_cov_valid = h->solver == DEKF_SOLVER_DIRECT;
     h->innov_valid = h->innov;
     h->win_steps = h->smoother ? K : 0;
-    if (instance_mode(h).restarted && h->smoother) {  // the largest window of the batch: the instance restarted longest ago (none at its local step 0),
-        const int Ta = T - h->inst.min_t0;  // or a paused one with the window it stands at
-        const int Tl = Ta > h->inst.max_frozen ? Ta : h->inst.max_frozen;
-        h->win_steps = Tl < 1 ? 0 : (Tl + 1 < h->c.N ? Tl + 1 : h->c.N);
-    }
+    if (instance_mode(h).restarted && h->smoother) h->win_steps = epoch_window_steps(h, T);
     return DEKF_OK;
 }
 
@@ -891,6 +902,7 @@ dekf_status dekf_create(const dekf_params* p, int batch, int device, void* strea
     }
     h->sp[0] = h->s;
     h->sp[1] = h->pipelined ? second_set(h->c, h->s, solve_slots) : h->s;
+    state_map(h->c, h->s, h->snap_map);
     int prio_least = 0, prio_greatest = 0;  // (of the streams the two modes create below)
     (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
     // (N = 1: the record folded at step T gets its gains AT step T.  DEKF_DEBUG_NO_EARLY_MARGINALIZE in the environment: diagnostic switch,
@@ -1152,6 +1164,141 @@ dekf_status dekf_get_instance_params(dekf_handle h, int b, dekf_params* out) {
     return DEKF_OK;
 }
 
+namespace {
+// what dekf_save_instances and dekf_load_instances ask of their arguments alike; the header a blob of n instances of h carries
+dekf_status snapshot_args(dekf_handle h, const char* fn, const int* idx, int n, const void* blob, size_t bytes) {
+    const std::string f(fn);
+    if (!h) return fail(DEKF_ERR_INVALID, "null handle");
+    if (!idx || !blob) return fail(DEKF_ERR_INVALID, (f + ": null idx or blob").c_str());
+    TRY(need_direct(h, fn, true));
+    if (n <= 0) return fail(DEKF_ERR_INVALID, (f + ": n must be positive").c_str());
+    std::vector<unsigned char> seen((size_t)h->c.B, 0);
+    if (!snapshot_indices_valid(idx, n, h->c.B, seen.data()))
+        return fail(DEKF_ERR_INVALID, (f + ": every index must lie in 0 .. B - 1 and be named once").c_str());
+    if (bytes < dekf_snapshot_bytes(h, n)) return fail(DEKF_ERR_INVALID, (f + ": the blob is smaller than dekf_snapshot_bytes(h, n)").c_str());
+    return DEKF_OK;
+}
+SnapHeader snapshot_header_of(const dekf_handle_s* h, int n) {
+    return snapshot_header(h->prm, h->snap_map, n, h->solver, h->smoother, h->cross, h->innov, h->gate_st.nis_leg_max);
+}
+const dekf_params* instance_params_of(const dekf_handle_s* h, int b) {
+    return instance_mode(h).clock == Clock::PARAM ? &h->inst.inst_prm[(size_t)b] : &h->prm;
+}
+// workgroups per instance of the snapshot kernels: a few instances are spread over the machine by the arrays of the map
+int snapshot_chunks(int n) { return n >= 512 ? 1 : (n >= 64 ? 4 : 16); }
+// device memory for the length of one call: the image of a host blob
+struct TempDev {
+    unsigned char* p = nullptr;
+    ~TempDev() { if (p) (void)hipFree(p); }
+};
+}  // namespace
+
+size_t dekf_snapshot_bytes(dekf_handle h, int n) {
+    if (!h || n <= 0 || h->c.est_type != 0 || h->pipelined || h->solver != DEKF_SOLVER_DIRECT) return 0;
+    return snap_header_bytes() + (size_t)n * snap_record_bytes(h->snap_map);
+}
+
+dekf_status dekf_save_instances(dekf_handle h, const int* idx, int n, void* blob, size_t bytes, dekf_mem where) {
+    TRY(snapshot_args(h, "dekf_save_instances", idx, n, blob, bytes));
+    HIPCHK(hipSetDevice(h->device));
+    TRY(quiesce(h));  // (what dekf_reset_instances waits for: the arrival cost computed ahead must have landed before it is copied)
+    const dekf_handle_s::Instances& in = h->inst;
+    const size_t hb = snap_header_bytes(), rb = snap_record_bytes(h->snap_map), N = (size_t)n;
+    // header | books of the n records | idx: built here, staged in one copy; the kernel writes the books at the head of every record
+    std::vector<unsigned char> host(hb + N * sizeof(SnapBooks) + N * sizeof(int), 0);
+    const SnapHeader hd = snapshot_header_of(h, n);
+    std::memcpy(host.data(), &hd, sizeof(hd));
+    SnapBooks* bk = (SnapBooks*)(host.data() + hb);
+    const bool epochs = in.t0 != nullptr;
+    for (size_t i = 0; i < N; ++i) {
+        snapshot_books(idx[i], epochs ? in.act_host.data() : nullptr, in.pz_step.data(), in.pz_count.data(), in.t0_host.data(),
+                       in.c0_host.data(), h->next_T, h->ekf_count, h->c.ekf_hist, &bk[i].step, &bk[i].count);
+        pack_noise(*instance_params_of(h, idx[i]), bk[i].noise);
+    }
+    std::memcpy(host.data() + hb + N * sizeof(SnapBooks), idx, N * sizeof(int));
+    TRY(ensure_stage(h, host.size()));
+    unsigned char* const stage = (unsigned char*)h->stage;
+    HIPCHK(hipMemcpyAsync(stage, host.data(), host.size(), hipMemcpyHostToDevice, h->stream));
+    TempDev tmp;
+    unsigned char* dst = (unsigned char*)blob;
+    if (where == DEKF_HOST) {
+        HIPCHK(hipMalloc((void**)&tmp.p, hb + N * rb));
+        dst = tmp.p;
+    }
+    HIPCHK(hipMemcpyAsync(dst, stage, hb, hipMemcpyDeviceToDevice, h->stream));
+    k_save_instances<<<dim3((unsigned)n, (unsigned)snapshot_chunks(n)), 256, 0, h->stream>>>(
+        h->snap_map, (const int*)(stage + hb + N * sizeof(SnapBooks)), (const SnapBooks*)(stage + hb), dst + hb, rb);
+    HIPCHK(hipGetLastError());
+    if (where == DEKF_HOST) HIPCHK(hipMemcpyAsync(blob, dst, hb + N * rb, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));  // (a host blob is there when the call returns; `host`, a local, is the source of the staging copy)
+    return DEKF_OK;
+}
+
+dekf_status dekf_load_instances(dekf_handle h, const int* idx, int n, const void* blob, size_t bytes, dekf_mem where) {
+    TRY(snapshot_args(h, "dekf_load_instances", idx, n, blob, bytes));
+    HIPCHK(hipSetDevice(h->device));
+    dekf_handle_s::Instances& in = h->inst;
+    const size_t hb = snap_header_bytes(), rb = snap_record_bytes(h->snap_map), N = (size_t)n;
+    const unsigned char* const src = (const unsigned char*)blob;
+    // everything is checked before anything is applied: the header, then the books of every record (a device blob's are copied to the
+    // host and waited for, as a device mask is)
+    SnapHeader got;
+    std::vector<SnapBooks> bk(N);
+    if (where == DEKF_HOST) std::memcpy(&got, src, sizeof(got));
+    else {
+        HIPCHK(hipMemcpyAsync(&got, src, sizeof(got), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    const SnapHeader want = snapshot_header_of(h, n);
+    if (got.magic != DEKF_SNAP_MAGIC) return fail(DEKF_ERR_INVALID, "dekf_load_instances: not a snapshot blob (magic)");
+    if (got.version != DEKF_SNAP_VERSION) return fail(DEKF_ERR_INVALID, "dekf_load_instances: the blob has another format version");
+    if (got.n != n) return fail(DEKF_ERR_INVALID, "dekf_load_instances: n is not the blob's n");
+    if (std::memcmp(&got, &want, sizeof(got)) != 0)
+        return fail(DEKF_ERR_INVALID, "dekf_load_instances: the blob's fingerprint is not this handle's (parameters outside the noise fields, settings, stores)");
+    if (where == DEKF_HOST)
+        for (size_t i = 0; i < N; ++i) std::memcpy(&bk[i], src + hb + i * rb, sizeof(SnapBooks));
+    else {
+        HIPCHK(hipMemcpy2DAsync(bk.data(), sizeof(SnapBooks), src + hb, rb, sizeof(SnapBooks), N, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    if (h->next_T >= DEKF_EPOCH_PAUSED) return fail(DEKF_ERR_ORDER, "dekf_load_instances: the handle has run 2^31 - 2^16 steps: dekf_reset it");
+    for (size_t i = 0; i < N; ++i) {
+        if (!snapshot_books_valid(bk[i].step, bk[i].count, h->c.ekf_hist))
+            return fail(DEKF_ERR_INVALID, "dekf_load_instances: a record's local step or EKF count is out of range");
+        double noise[DEKF_SNAP_NOISE];
+        pack_noise(*instance_params_of(h, idx[i]), noise);
+        if (std::memcmp(noise, bk[i].noise, sizeof(noise)) != 0)
+            return fail(DEKF_ERR_INVALID, "dekf_load_instances: a record's noise fields are not those of the instance it loads into "
+                                          "(dekf_reset_instances, then dekf_set_instance_params gives the slot the set first)");
+    }
+    TRY(quiesce(h));
+    TRY(in.ensure(h));
+    TempDev tmp;
+    const unsigned char* recs = src + hb;
+    if (where == DEKF_HOST) {
+        HIPCHK(hipMalloc((void**)&tmp.p, N * rb));
+        HIPCHK(hipMemcpyAsync(tmp.p, src + hb, N * rb, hipMemcpyHostToDevice, h->stream));
+        recs = tmp.p;
+    }
+    const int* didx = idx;
+    TRY(ensure_stage(h, N * sizeof(int)));
+    TRY(stage_in(h, 0, &didx, N));
+    k_load_instances<<<dim3((unsigned)n, (unsigned)snapshot_chunks(n)), 256, 0, h->stream>>>(h->snap_map, didx, recs, rb);
+    HIPCHK(hipGetLastError());
+    // the books: every loaded instance is active on the epochs of a resume (mhe_snapshot_core.h: load_instance)
+    const size_t B = (size_t)h->c.B;
+    for (size_t i = 0; i < N; ++i)
+        load_instance(idx[i], bk[i].step, bk[i].count, in.act_host.data(), in.t0_host.data(), in.c0_host.data(), h->next_T, h->ekf_count,
+                      h->c.ekf_hist);
+    HIPCHK(hipMemcpyAsync(in.t0, in.t0_host.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(in.c0, in.c0_host.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));  // (the caller's idx and a host blob are sources of the copies; the host's epochs change at the next call)
+    in.bounds();
+    in.restarted = true;  // (the epoch twins from here on, as after a restart)
+    if (h->smoother && h->win_steps) h->win_steps = epoch_window_steps(h, h->next_T - 1);  // (the loaded windows count from now on)
+    return DEKF_OK;
+}
+
 dekf_status dekf_sync(dekf_handle h) {
     if (!h) return fail(DEKF_ERR_INVALID, "null handle");
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -1401,7 +1548,10 @@ dekf_status dekf_set_solver(dekf_handle h, int solver) {
         const DirectKernel* k = direct_kernel(h->c.L, h->c.ft, h->c.N);
         if (!k) return fail(DEKF_ERR_INVALID, "no direct solve kernel for this shape");
         HIPCHK(hipSetDevice(h->device));
-        if (!h->mhe_cov) TRY(dev_alloc(h, (size_t)h->c.B * h->c.ns * h->c.ns * sizeof(double), &h->mhe_cov));
+        if (!h->mhe_cov) {
+            TRY(dev_alloc(h, (size_t)h->c.B * h->c.ns * h->c.ns * sizeof(double), &h->mhe_cov));
+            h->snap_map.add(h->mhe_cov, h->c.ns * h->c.ns, 8, SNAP_INSTANCE_MAJOR, SNAP_TAG_COV);
+        }
         h->direct = k;
         h->lds_direct = (size_t)DirectScratch::len(h->c.ns) * sizeof(double);
     }
@@ -1429,6 +1579,9 @@ dekf_status dekf_set_smoother(dekf_handle h, int on) {
         TRY(dev_alloc(h, B * (N * ns + (2 * N - 1) * ns * ns) * sizeof(double), &h->win.x));  // x | cov | t1 in one block
         h->win.cov = h->win.x + B * N * ns;
         h->win.t1 = h->win.cov + B * N * ns * ns;
+        h->snap_map.add(h->win.x, h->c.N * h->c.ns, 8, SNAP_INSTANCE_MAJOR, SNAP_TAG_WIN_X);
+        h->snap_map.add(h->win.cov, h->c.N * h->c.ns * h->c.ns, 8, SNAP_INSTANCE_MAJOR, SNAP_TAG_WIN_COV);
+        h->snap_map.add(h->win.t1, (h->c.N - 1) * h->c.ns * h->c.ns, 8, SNAP_INSTANCE_MAJOR, SNAP_TAG_WIN_T1);
     }
     h->smoother = on != 0;
     if (!on) h->cross = false;  // the cross-covariances are the smoother's: switched off with it
@@ -1445,6 +1598,7 @@ dekf_status dekf_set_window_cross(dekf_handle h, int on) {
         HIPCHK(hipSetDevice(h->device));
         const size_t B = (size_t)h->c.B, N = (size_t)h->c.N, ns = (size_t)h->c.ns;
         TRY(dev_alloc(h, B * N * ns * ns * sizeof(double), &h->cross_st.newest));  // (the lag-one blocks take the smoother's t1 store)
+        h->snap_map.add(h->cross_st.newest, h->c.N * h->c.ns * h->c.ns, 8, SNAP_INSTANCE_MAJOR, SNAP_TAG_CROSS);
     }
     h->cross = on != 0;
     h->win_steps = 0;
@@ -1492,6 +1646,11 @@ dekf_status dekf_set_innovation(dekf_handle h, int on) {
         h->innov_st.nis = h->innov_st.S + B * nm * nm;
         h->innov_st.nis_leg = h->innov_st.nis + B;
         h->innov_st.loglik = h->innov_st.nis_leg + B * L;
+        h->snap_map.add(h->innov_st.nu, (int)nm, 8, SNAP_INSTANCE_MAJOR, SNAP_TAG_INNOV_NU);
+        h->snap_map.add(h->innov_st.S, (int)(nm * nm), 8, SNAP_INSTANCE_MAJOR, SNAP_TAG_INNOV_S);
+        h->snap_map.add(h->innov_st.nis, 1, 8, SNAP_INSTANCE_MAJOR, SNAP_TAG_INNOV_NIS);
+        h->snap_map.add(h->innov_st.nis_leg, (int)L, 8, SNAP_INSTANCE_MAJOR, SNAP_TAG_INNOV_NIS_LEG);
+        h->snap_map.add(h->innov_st.loglik, 1, 8, SNAP_INSTANCE_MAJOR, SNAP_TAG_INNOV_LOGLIK);
     }
     h->innov = on != 0;
     h->innov_valid = false;
@@ -1511,6 +1670,7 @@ dekf_status dekf_set_innovation_gate(dekf_handle h, double nis_leg_max) {
         const size_t n = (size_t)h->c.B * h->c.L * sizeof(int);
         TRY(dev_alloc(h, n, &h->gate_st.gated));
         HIPCHK(hipMemsetAsync(h->gate_st.gated, 0, n, h->stream));
+        h->snap_map.add(h->gate_st.gated, h->c.L, 4, SNAP_INSTANCE_MAJOR, SNAP_TAG_GATED);
     }
     h->gate_st.nis_leg_max = nis_leg_max;
     return DEKF_OK;

@@ -7,6 +7,7 @@
 
 #include "cfg.h"
 #include "ekf_core.h"
+#include "mhe_snapshot_core.h"
 
 namespace dekf {
 
@@ -94,30 +95,52 @@ inline const char* check_noise(const dekf_params& p) {
     return nullptr;
 }
 
-// p with the noise fields of `from` (see fill_noise): what dekf_get_instance_params hands out
+// The fields of dekf_params, each named once: the noise fields (see fill_noise; all arrays of doubles) and every other one — structure,
+// rates, N, the osqp.* block, contact_effort_threshold, the IMU-to-body transform, the form switches and launch tuning
+#define DEKF_NOISE_FIELDS(X)                                                                                                          \
+    X(p_init_std) X(v_init_std) X(foot_init_std) X(accel_bias_init_std) X(p_process_std) X(accel_input_std) X(gyro_input_std)         \
+    X(accel_bias_std) X(joint_position_std) X(joint_velocity_std) X(foot_slide_std) X(foot_swing_std) X(vo_p_std) X(ekf_init_std)     \
+    X(ekf_process_std) X(ekf_gravity_meas_std) X(ekf_vo_meas_std) X(ekf_quaternion_init)
+#define DEKF_STRUCTURE_FIELDS(X)                                                                                                      \
+    X(quaternion_ib) X(p_ib) X(num_legs) X(joints_per_leg) X(leg_odom_type) X(contact_effort_threshold) X(rate) X(N) X(est_type)      \
+    X(rho) X(alpha) X(delta) X(sigma) X(verbose) X(adapt_rho) X(polish) X(max_qp_iter) X(rel_tol) X(abs_tol) X(prim_tol) X(dual_tol)  \
+    X(time_limit) X(scaling_iters) X(check_termination) X(adaptive_rho_interval) X(adaptive_rho_tolerance) X(ekf_rate) X(ekf_history) \
+    X(polish_refine_iter) X(arrival_cost_form) X(solve_pipeline) X(solve_workgroups_per_cu) X(polish_accept_osqp)
+
+// p with the noise fields of `from`: what dekf_get_instance_params hands out
 inline dekf_params with_noise_of(dekf_params p, const dekf_params& from) {
-#define DEKF_COPY_(F) std::memcpy(p.F, from.F, sizeof(p.F))
-    DEKF_COPY_(p_init_std); DEKF_COPY_(v_init_std); DEKF_COPY_(foot_init_std); DEKF_COPY_(accel_bias_init_std);
-    DEKF_COPY_(p_process_std); DEKF_COPY_(accel_input_std); DEKF_COPY_(gyro_input_std); DEKF_COPY_(accel_bias_std);
-    DEKF_COPY_(joint_position_std); DEKF_COPY_(joint_velocity_std); DEKF_COPY_(foot_slide_std); DEKF_COPY_(foot_swing_std);
-    DEKF_COPY_(vo_p_std); DEKF_COPY_(ekf_init_std); DEKF_COPY_(ekf_process_std); DEKF_COPY_(ekf_gravity_meas_std);
-    DEKF_COPY_(ekf_vo_meas_std); DEKF_COPY_(ekf_quaternion_init);
+#define DEKF_COPY_(F) std::memcpy(p.F, from.F, sizeof(p.F));
+    DEKF_NOISE_FIELDS(DEKF_COPY_)
 #undef DEKF_COPY_
     return p;
 }
 
-// every field that is NOT a noise field is the same in a and b (field by field: the struct has padding): structure, rates, N, the
-// osqp.* block, contact_effort_threshold, the IMU-to-body transform, the form switches and launch tuning
+// every field that is NOT a noise field is the same in a and b (field by field: the struct has padding)
 inline bool same_but_noise(const dekf_params& a, const dekf_params& b) {
-#define DEKF_SAME_(F) (std::memcmp(&a.F, &b.F, sizeof(a.F)) == 0)
-    return DEKF_SAME_(quaternion_ib) && DEKF_SAME_(p_ib) && DEKF_SAME_(num_legs) && DEKF_SAME_(joints_per_leg) && DEKF_SAME_(leg_odom_type) &&
-           DEKF_SAME_(contact_effort_threshold) && DEKF_SAME_(rate) && DEKF_SAME_(N) && DEKF_SAME_(est_type) && DEKF_SAME_(rho) &&
-           DEKF_SAME_(alpha) && DEKF_SAME_(delta) && DEKF_SAME_(sigma) && DEKF_SAME_(verbose) && DEKF_SAME_(adapt_rho) && DEKF_SAME_(polish) &&
-           DEKF_SAME_(max_qp_iter) && DEKF_SAME_(rel_tol) && DEKF_SAME_(abs_tol) && DEKF_SAME_(prim_tol) && DEKF_SAME_(dual_tol) &&
-           DEKF_SAME_(time_limit) && DEKF_SAME_(scaling_iters) && DEKF_SAME_(check_termination) && DEKF_SAME_(adaptive_rho_interval) &&
-           DEKF_SAME_(adaptive_rho_tolerance) && DEKF_SAME_(ekf_rate) && DEKF_SAME_(ekf_history) && DEKF_SAME_(polish_refine_iter) &&
-           DEKF_SAME_(arrival_cost_form) && DEKF_SAME_(solve_pipeline) && DEKF_SAME_(solve_workgroups_per_cu) && DEKF_SAME_(polish_accept_osqp);
+    bool same = true;
+#define DEKF_SAME_(F) same = same && std::memcmp(&a.F, &b.F, sizeof(a.F)) == 0;
+    DEKF_STRUCTURE_FIELDS(DEKF_SAME_)
 #undef DEKF_SAME_
+    return same;
+}
+
+// the noise fields of p as a record of a snapshot holds them (SnapBooks::noise), in the order of the list
+#define DEKF_COUNT_(F) +sizeof(dekf_params::F) / sizeof(double)
+static_assert(0 DEKF_NOISE_FIELDS(DEKF_COUNT_) == DEKF_SNAP_NOISE, "SnapBooks::noise holds every noise field");
+#undef DEKF_COUNT_
+inline void pack_noise(const dekf_params& p, double* out) {
+#define DEKF_PACK_(F) std::memcpy(out, p.F, sizeof(p.F)); out += sizeof(p.F) / sizeof(double);
+    DEKF_NOISE_FIELDS(DEKF_PACK_)
+#undef DEKF_PACK_
+}
+// p with the noise fields and the padding zeroed: the part of a snapshot's fingerprint that the parameters decide
+inline dekf_params structure_of(const dekf_params& p) {
+    dekf_params q;
+    std::memset(&q, 0, sizeof(q));
+#define DEKF_COPY_(F) std::memcpy(&q.F, &p.F, sizeof(q.F));
+    DEKF_STRUCTURE_FIELDS(DEKF_COPY_)
+#undef DEKF_COPY_
+    return q;
 }
 
 // returns nullptr when ok, else a message
@@ -213,6 +236,56 @@ inline DevState second_set(const DevCfg& c, const DevState& s, int solve_slots) 
     t.pri_res += B; t.dua_res += B;
     t.prof += DEKF_PROF_SLOTS * B;
     return t;
+}
+
+// The state map of an in-order handle (copies = 1): every persistent per-instance array of alloc_state with its elements per instance
+// and its indexing kind (mhe_snapshot_core.h), tags 0, 1, ... in this order.  Left out by name, because they belong to a solve slot or
+// to a launch and not to an instance: gws, queue, prof.  An array that is dead between two updates is listed all the same.  A new array
+// of alloc_state gets its line here (tests/test_instance_snapshot.py adds the bytes up).
+inline void state_map(const DevCfg& c, const DevState& s, StateMap& m) {
+    const int L = c.L, nj = c.nj, ns = c.ns;
+    m.n = 0;
+    m.B = c.B;
+    int tag = 0;
+    auto D = [&](double* p, int per, int kind = SNAP_INSTANCE_MAJOR) { m.add(p, per, (int)sizeof(double), kind, tag++); };
+    auto I = [&](int* p, int per) { m.add(p, per, (int)sizeof(int), SNAP_INSTANCE_MAJOR, tag++); };
+    D(s.imu_t, 1); D(s.accel, 3); D(s.gyro, 3);
+    D(s.p_foot, 3 * L); D(s.J, 3 * L * nj); D(s.qdot, L * nj); D(s.contact, L);
+    D(s.quat, 4);
+    I(s.vo_flag, 1); D(s.vo_tpre, 1); D(s.vo_tnow, 1); D(s.vo_dp, 3);
+    I(s.ekf_vo_flag, 1); D(s.ekf_vo_t, 1); D(s.ekf_vo_q, 4);
+    D(s.ekf_q, 4, SNAP_ELEMENT_MAJOR); D(s.ekf_P, 16, SNAP_ELEMENT_MAJOR); D(s.ekf_hist, c.ekf_hist * EKF_HIST_REC, SNAP_ELEMENT_MAJOR);
+    D(s.st_time, c.ring); D(s.st_R, c.ring * 9); I(s.st_dtime, c.ring);
+    D(s.rec, c.wcap * c.rec); D(s.Mp, ns * ns); D(s.np_, ns);
+    D(s.Mp_next, ns * ns); D(s.np_next, ns); I(s.marg_tag, 1);
+    D(s.snap, c.snap_len);
+    D(s.wp, 12); D(s.wpt, 4); I(s.wp_count, 1);
+    D(s.p_vo, 3); I(s.vo_ins_idx, 1); I(s.vo_ins_dtime, 1);
+    D(s.kf_x, ns); D(s.kf_C, ns * ns);
+    D(s.x_mhe, ns); D(s.v_b, 3);
+    I(s.status, 1); I(s.iters, 1); I(s.rho_updates, 1); I(s.polish_status, 1);
+    D(s.pri_res, 1); D(s.dua_res, 1);
+}
+// bytes per instance of what state_map leaves out by name, of a handle of B instances with `solve_slots` solver slabs (copies = 1)
+inline size_t state_map_excluded_bytes(const DevCfg& c, int solve_slots) {
+    Gws g;
+    g.init(c.N, c.L, c.ft, c.gws_wt);
+    return ((size_t)solve_slots * g.total + (size_t)DEKF_PROF_SLOTS * c.B) * sizeof(double) + 2 * sizeof(int);
+}
+// the header of a blob of n instances of a handle with these parameters, settings and stores
+inline SnapHeader snapshot_header(const dekf_params& p, const StateMap& m, int n, int solver, bool smoother, bool cross, bool innov,
+                                  double nis_leg_max) {
+    SnapHeader hd;
+    std::memset(&hd, 0, sizeof(hd));
+    hd.magic = DEKF_SNAP_MAGIC;
+    hd.version = DEKF_SNAP_VERSION;
+    hd.n = n;
+    hd.rec_bytes = snap_record_bytes(m);
+    hd.stores = m.stores();
+    hd.solver = solver; hd.smoother = smoother; hd.cross = cross; hd.innov = innov;
+    hd.nis_leg_max = nis_leg_max;
+    hd.structure = structure_of(p);
+    return hd;
 }
 
 }  // namespace dekf

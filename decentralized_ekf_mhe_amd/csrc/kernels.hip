@@ -14,6 +14,7 @@
 //   k_reset_instances, k_*_ep   restarting single instances of a direct handle (dekf_reset_instances, mhe_epoch_core.h)
 //   k_*_pp            the same with noise parameters per instance (dekf_set_instance_params, mhe_params_core.h)
 //   k_*_act           the tick, assemble, VO latch and fold of a handle that has paused an instance (dekf_set_active, mhe_pause_core.h)
+//   k_save_instances, k_load_instances   single instances to and from a snapshot blob (dekf_save_instances, mhe_snapshot_core.h)
 #include <hip/hip_runtime.h>
 
 #include "cfg.h"
@@ -27,6 +28,7 @@
 #include "mhe_gate_core.h"
 #include "mhe_params_core.h"
 #include "mhe_pause_core.h"
+#include "mhe_snapshot_core.h"
 #include "mhe_solve_core.h"
 
 using namespace dekf;
@@ -136,6 +138,12 @@ extern "C" {
 #define DEKF_GATE_KERNELS 1
 #else
 #define DEKF_GATE_KERNELS 0
+#endif
+// ... and the snapshot kernels (dekf_save_instances, dekf_load_instances) only with bit 8192: the same again
+#if !defined(DEKF_KSET_ONLY) || (defined(DEKF_KSET) && (DEKF_KSET & 8192))
+#define DEKF_SNAPSHOT_KERNELS 1
+#else
+#define DEKF_SNAPSHOT_KERNELS 0
 #endif
 #if DEKF_MISC_KERNELS
 __global__ void __launch_bounds__(64) k_ekf_tick(DevCfg c, DevState s, int count) {
@@ -368,6 +376,24 @@ DEKF_GATE_KERNEL(3)
 DEKF_GATE_KERNEL(4)
 #undef DEKF_GATE_KERNEL
 #endif  // DEKF_GATE_KERNELS
+
+#if DEKF_SNAPSHOT_KERNELS
+// The snapshot kernels (dekf_save_instances, dekf_load_instances; mhe_snapshot_core.h).  A grid of (n, chunks) workgroups of 256 lanes:
+// workgroup (i, j) walks the state map m for instance idx[i] and moves every chunks-th array, from j on, between the handle's state
+// and record i of the blob (recs: its first record; rec_bytes apart).  The record side of every copy is contiguous, consecutive lanes
+// on consecutive elements; so is the state side of an instance-major array; an element-major one (the EKF state and its history, a
+// lane per instance in k_ekf_tick) is strided by B there.  books: the host-side books of the n records, which the save writes at the
+// head of each.  A set of their own (bit 8192), carried by every build without -DDEKF_KSET_ONLY.
+__global__ void __launch_bounds__(256) k_save_instances(StateMap m, const int* __restrict__ idx, const SnapBooks* __restrict__ books,
+                                                        unsigned char* recs, size_t rec_bytes) {
+    const size_t i = blockIdx.x;
+    snapshot_instance<true>(m, idx[i], recs + i * rec_bytes, books + i, (int)blockIdx.y, (int)gridDim.y);
+}
+__global__ void __launch_bounds__(256) k_load_instances(StateMap m, const int* __restrict__ idx, const unsigned char* recs, size_t rec_bytes) {
+    const size_t i = blockIdx.x;
+    snapshot_instance<false>(m, idx[i], const_cast<unsigned char*>(recs) + i * rec_bytes, nullptr, (int)blockIdx.y, (int)gridDim.y);
+}
+#endif  // DEKF_SNAPSHOT_KERNELS
 
 #if DEKF_MISC_KERNELS
 __global__ void k_gap() {}

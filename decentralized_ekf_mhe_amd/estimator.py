@@ -211,6 +211,43 @@ class BatchedEstimator:
         capi.check(self.lib.dekf_get_instance_params(self.h, int(b), C.byref(out)))
         return out
 
+    def snapshot_bytes(self, n):
+        """bytes of a blob of n instances of this handle (dekf_snapshot_bytes); 0 on a handle that cannot save"""
+        return int(self.lib.dekf_snapshot_bytes(self.h, int(n)))
+
+    def save_instances(self, idx, device=False):
+        """the instances `idx` (a sequence of distinct ints) as one opaque blob (dekf_save_instances; a direct handle, between
+        update(T - 1) and update(T)): a uint8 numpy array, or with device=True a uint8 torch CUDA tensor written by the GPU alone.
+        Saving changes nothing on the handle.  The blob loads into any slots of any handle with the same parameters outside the noise
+        fields and the same settings (load_instances): a checkpoint, a migration to another batch, GPU or rank, or a fork"""
+        ix = np.ascontiguousarray(idx, np.int32)
+        nbytes = max(self.snapshot_bytes(len(ix)), 1)
+        if device:
+            import torch
+            blob = torch.empty(nbytes, dtype=torch.uint8, device=f"cuda:{self.device}")
+            torch.cuda.synchronize()
+            ptr, where = C.c_void_p(blob.data_ptr()), capi.DEKF_DEVICE
+        else:
+            blob = np.zeros(nbytes, np.uint8)
+            ptr, where = C.c_void_p(blob.ctypes.data), capi.DEKF_HOST
+        capi.check(self.lib.dekf_save_instances(self.h, C.c_void_p(ix.ctypes.data), len(ix), ptr, nbytes, where))
+        return blob
+
+    def load_instances(self, idx, blob):
+        """make instance idx[i] the i-th saved instance of `blob` (dekf_load_instances; uint8, numpy or a torch CUDA tensor that is
+        complete on its stream): it is active and goes on, bit for bit, as its source would have.  Push IMU and leg samples before its
+        next tick or update.  A blob of another configuration, or noise fields that are not the slot's, are refused and nothing is
+        applied"""
+        ix = np.ascontiguousarray(idx, np.int32)
+        if isinstance(blob, np.ndarray):
+            assert blob.dtype == np.uint8 and blob.flags["C_CONTIGUOUS"]
+            ptr, where, nbytes = C.c_void_p(blob.ctypes.data), capi.DEKF_HOST, blob.nbytes
+        else:
+            import torch
+            assert isinstance(blob, torch.Tensor) and blob.dtype == torch.uint8 and blob.is_contiguous()
+            ptr, where, nbytes = C.c_void_p(blob.data_ptr()), (capi.DEKF_DEVICE if blob.is_cuda else capi.DEKF_HOST), blob.numel()
+        capi.check(self.lib.dekf_load_instances(self.h, C.c_void_p(ix.ctypes.data), len(ix), ptr, nbytes, where))
+
     def sync(self):
         capi.check(self.lib.dekf_sync(self.h))
 

@@ -28,6 +28,8 @@
 #ifndef DEKF_H
 #define DEKF_H
 
+#include <stddef.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -546,6 +548,60 @@ dekf_status dekf_get_innovation(dekf_handle h, double* innov, double* innov_cov,
  * Not part of this interface: a bound per instance; a history of decisions (gated is the last update's); smoothing handles. */
 dekf_status dekf_set_innovation_gate(dekf_handle h, double nis_leg_max);
 dekf_status dekf_get_innovation_gate(dekf_handle h, double* nis_leg_max, int* gated, dekf_mem where);
+
+/* ---- snapshots of single instances (direct handles): one robot leaves its slot, its handle, its process -----------------------
+ * Three more additive symbols: DEKF_ABI_VERSION and dekf_params are unchanged, and a caller that never calls them launches exactly the
+ * kernels of before and gets the same bits.  An instance can be restarted, paused and given its own noise; with these it can also be
+ * checkpointed and brought back after a process restart, migrated to another handle, batch size, GPU or rank (dekf_allgather_vb
+ * shards a fleet over ranks; this rebalances the shards), and forked: copied into a second slot to run two hypotheses side by side
+ * from that point, with the per-tick loglik of dekf_get_innovation as the score between them.
+ * A blob is opaque and self-describing: a fixed header (a magic, a format version, a fingerprint, n and the bytes per instance)
+ * followed by n contiguous per-instance records in the order of idx.  A record holds the instance's LOCAL step and LOCAL EKF count
+ * (the count reduced as a resume stores it), its noise fields as dekf_get_instance_params returns them, and every persistent
+ * per-instance array of the handle: latches, EKF state and history, sample stack, window records, arrival cost (the one computed
+ * ahead included), tags, outputs, and the handle's optional stores that are allocated: Cov(x_T), the smoother's window stores, the
+ * cross store, the five innovation arrays and gated.  The handle's own step, EKF tick count and epochs are never stored, so a record
+ * loads into any slot of any compatible handle at any step.  The fingerprint is every field of dekf_params outside the noise fields
+ * and every setting: solver, smoother, cross, innovation, the gate and its bound.  A blob is valid for the library build that wrote
+ * it; it is not a file format across versions.
+ * dekf_snapshot_bytes(h, n): bytes of a blob of n instances of h; 0 on a handle that cannot save (ADMM, KF, pipelined, null) and for
+ * n <= 0.  idx[n] is always a host pointer; blob is host or device memory, as `where` says.
+ * dekf_save_instances(h, idx, n, blob, bytes, where):
+ *  - Where: a direct handle without solve_pipeline.  DEKF_ERR_INVALID on ADMM, KF and pipelined handles; DEKF_ERR_ORDER before
+ *    dekf_initialize.
+ *  - When: anywhere between dekf_update(h, T0 - 1) and dekf_update(h, T0); on a two-rate handle before, between or behind the EKF
+ *    ticks of that gap.  The handle's stream waits for what dekf_reset_instances waits for (the arrival cost computed ahead has
+ *    landed before it is copied).  The call returns when the blob is written, host or device.
+ *  - Any instance may be saved.  An active one: its current local step and count; a paused one: those it stands at; one restarted
+ *    and not yet initialised: local tick -1.
+ *  - Saving changes nothing: the handle keeps its kernels (dekf_solve_kernel_name) and every bit of every later output.
+ *  - DEKF_ERR_INVALID, with nothing written: a null handle, idx or blob; n <= 0; an index outside 0 .. B - 1; an index named twice;
+ *    bytes below dekf_snapshot_bytes(h, n).
+ * dekf_load_instances(h, idx, n, blob, bytes, where): where and when as for saving, on an initialised handle.  The header and the
+ * records' counters and noise fields of a device blob are copied to the host and waited for, as a device mask is.
+ *  - Checks; any failure is DEKF_ERR_INVALID and then NOTHING is applied.  Magic, format version and fingerprint must match; n must
+ *    be the blob's n; bytes at least dekf_snapshot_bytes(h, n); the indices as for saving; and the noise fields of record i must
+ *    equal, byte for byte, those instance idx[i] has now: the handle's own on a handle without a parameter table, else the slot is
+ *    first given the set by dekf_reset_instances, then dekf_set_instance_params.  A difference is refused, never ignored.
+ *  - After the load instance idx[i] IS the saved instance, and it is active.  Every getter returns the saved values to the bit:
+ *    dekf_get, dekf_get_ekf_cov, dekf_get_mhe_cov, dekf_get_solver_info, its first K_b entries of dekf_get_window and
+ *    dekf_get_window_cross, dekf_get_innovation and gated of dekf_get_innovation_gate (a getter that refuses before the handle's first
+ *    update still does); dekf_get_instance_ticks returns its local step.  Its epochs are those of a resume: t0 = next step - local
+ *    step, which is negative when an old robot loads into a young handle, and c0 = EKF tick count - local count.  A record saved at
+ *    local tick -1 loads as a freshly restarted instance: its first update is its dekf_initialize.
+ *  - IMU and leg samples are pushed at least once between the load and the instance's next tick or update (the rule of
+ *    dekf_reset_instances).  From then on every output of the instance is bit-identical to the source instance on an uninterrupted
+ *    handle fed the same samples, ticks and updates in order, whatever the batch size of the destination, the step it stands at, and
+ *    whether the blob went through the host.
+ *  - Instances not named keep every bit of every output at every later step.
+ *  - After the first load the handle launches the epoch twins (_ep, or _pp with a table), exactly as after a restart, until
+ *    dekf_reset, which forgets loaded instances like everything else.
+ *  - Forking: two indices of one handle may be given copies of one record by two loads of the same blob.
+ * Not part of this interface: ADMM, KF and pipelined handles; blobs across library versions; a handle whose parameters outside the
+ * noise fields or whose settings differ in any field; changing an instance's noise by loading it. */
+size_t dekf_snapshot_bytes(dekf_handle h, int n);
+dekf_status dekf_save_instances(dekf_handle h, const int* idx, int n, void* blob, size_t bytes, dekf_mem where);
+dekf_status dekf_load_instances(dekf_handle h, const int* idx, int n, const void* blob, size_t bytes, dekf_mem where);
 
 /* status[B] values written by dekf_update */
 #define DEKF_SOLVE_NONE 0       /* no solve yet (T = 0) */

@@ -34,7 +34,12 @@ twins with every instance active (`ep`, the yardstick), then for every fraction 
 it (0: one instance paused and resumed in the same gap, so the handle launches the *_act kernels with nobody paused), and runs again
 (`paused_F`); dekf_reset brings the handle back, and the runs alternate --repeat times in one process.  One JSON line per shape
 (--out: profiles/r13_pause_bench.jsonl).
-    python tools/direct_bench.py go1 --epoch --paused 0,0.5,0.9 --modes direct,direct_smooth,direct_cross --steps 80 --repeat 3"""
+    python tools/direct_bench.py go1 --epoch --paused 0,0.5,0.9 --modes direct,direct_smooth,direct_cross --steps 80 --repeat 3
+--snapshot measures dekf_save_instances and dekf_load_instances: per mode ONE handle runs past its window fill, then saves all B
+instances to a device blob and loads them back into their own slots, --repeat times, each call between two events on the handle's
+stream; beside them one device-to-device hipMemcpyAsync of the blob's byte count on the same stream, the yardstick the two kernels are
+read against.  One JSON line per shape (--out: profiles/r14_snapshot_bench.jsonl).
+    python tools/direct_bench.py go1 --snapshot --modes direct_smooth --repeat 5"""
 import argparse
 import json
 import os
@@ -231,6 +236,52 @@ def pause_runs(p, B, sd, steps, mode, repeat, fractions):
     return out
 
 
+def snapshot_runs(p, B, sd, mode, repeat):
+    """ms of saving all instances to a device blob, of loading them back, and of one device-to-device copy of as many bytes"""
+    import numpy as np
+    W = max(p.N + 10, 64)
+    est = BatchedEstimator(p, B, **MODES[mode])
+    for k in range(W):
+        est.push_stream_step(sd, k)
+        est.step(k)
+    est.sync()
+    idx = np.arange(B, dtype=np.int32)
+    stream = torch.cuda.ExternalStream(est.lib.dekf_stream(est.h))
+    nbytes, per_instance = est.snapshot_bytes(B), est.snapshot_bytes(2) - est.snapshot_bytes(1)
+    twin = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    out = {"save_ms": [], "load_ms": [], "memcpy_ms": []}
+
+    def ms(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        r = fn()
+        b.record(stream)
+        b.synchronize()
+        return a.elapsed_time(b), r
+
+    for _ in range(repeat + 1):   # (the first round is the warm-up: first launch of both kernels, first touch of both buffers)
+        t_save, blob = ms(lambda: est.save_instances(idx, device=True))
+        t_load, _ = ms(lambda: est.load_instances(idx, blob))
+        with torch.cuda.stream(stream):
+            t_copy, _ = ms(lambda: twin.copy_(blob, non_blocking=True))
+        assert torch.equal(twin, blob)
+        for key, v in (("save_ms", t_save), ("load_ms", t_load), ("memcpy_ms", t_copy)):
+            out[key].append(v)
+    for k in range(W, W + 4):     # the loaded handle goes on
+        est.push_stream_step(sd, k)
+        est.step(k)
+    assert float((est.get()["status"] == 1).mean()) == 1.0 and est.solve_kernel_name(True).endswith("_ep")
+    est.close()
+    res = {"bytes": nbytes, "bytes_per_instance": per_instance}
+    for key, v in out.items():
+        v = v[1:]
+        res[key] = {"median": float(np.median(v)), "min": min(v), "max": max(v), "all": v}
+    res["save_GB_per_s"] = nbytes / res["save_ms"]["median"] / 1e6
+    res["load_GB_per_s"] = nbytes / res["load_ms"]["median"] / 1e6
+    res["memcpy_GB_per_s"] = nbytes / res["memcpy_ms"]["median"] / 1e6
+    return res
+
+
 def distinct_sets(p, B):
     """B parameter sets, no two alike: every std of the noise fields scaled by a factor of its own in [0.8, 1.25]"""
     fields = ("p_init_std", "v_init_std", "foot_init_std", "accel_bias_init_std", "p_process_std", "accel_input_std", "gyro_input_std",
@@ -288,12 +339,15 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--epoch", action="store_true", help="the same handle before and after a first dekf_reset_instances")
     ap.add_argument("--instance-params", action="store_true", help="the same handle without and with a table of B distinct parameter sets")
+    ap.add_argument("--snapshot", action="store_true", help="dekf_save_instances / dekf_load_instances of the whole batch against a device-to-device copy")
     ap.add_argument("--paused", default=None, help="with --epoch: fractions of the batch to pause (dekf_set_active), e.g. 0,0.5,0.9")
     a = ap.parse_args()
     modes = a.modes.split(",")
     fractions = [float(f) for f in a.paused.split(",")] if a.paused else []
     if fractions and not a.epoch:
         ap.error("--paused goes with --epoch")
+    if a.out is None and a.snapshot:
+        a.out = os.path.join(ROOT, "profiles", "r14_snapshot_bench.jsonl")
     if a.out is None and fractions:
         a.out = os.path.join(ROOT, "profiles", "r13_pause_bench.jsonl")
     if a.out is None and a.instance_params:
@@ -311,6 +365,16 @@ def main():
         p.ekf_rate = p.rate
         for k, v in kw.items():
             setattr(p, k, v)
+        if a.snapshot:
+            sd = streams_to_device(make_streams(p, B, max(p.N + 10, 64) + 4))
+            line = {"shape": name, "batch": B, "N": int(p.N), "repeat": a.repeat, "snapshot": True}
+            line.update({mode: snapshot_runs(p, B, sd, mode, a.repeat) for mode in modes})
+            print(json.dumps(line), flush=True)
+            with open(a.out, "a") as f:
+                f.write(json.dumps(line) + "\n")
+            del sd
+            torch.cuda.empty_cache()
+            continue
         if a.instance_params:
             sd = streams_to_device(make_streams(p, B, max(p.N + 10, 64) + 2 * a.steps))
             line = {"shape": name, "batch": B, "N": int(p.N), "steps": a.steps, "repeat": a.repeat, "instance_params": True}
