@@ -64,7 +64,8 @@ PROTOTYPES = {
     "dekf_get_innovation": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int]),
     "dekf_set_innovation_gate": (C.c_int, [_vp, C.c_double]),
     "dekf_get_innovation_gate": (C.c_int, [_vp, _dp, _vp, C.c_int]),
-    "dekf_snapshot_bytes": (C.c_size_t, [_vp, C.c_int]),
+    "dekf_set_gate_smoother": (C.c_int, [_vp, C.c_int]),
+    "dekf_snapshot_bytes":(C.c_size_t, [_vp, C.c_int]),
     "dekf_save_instances": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_size_t, C.c_int]),
     "dekf_load_instances": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_size_t, C.c_int]),
     "dekf_timing_enable":(C.c_int, [_vp, C.c_int]),

@@ -1,9 +1,9 @@
 #!/bin/bash
 # Builds libdekf.so (the C-ABI shared library, gfx950 only) in-tree.
-#   bash build.sh                                            the product: every kernel, compiled as 15 translation units in parallel
+#   bash build.sh                                            the product: every kernel, compiled as 16 translation units in parallel
 #   DEKF_OUT=libdekf_prof.so DEKF_UNITY=1 bash build.sh -DDEKF_PROFILE -DDEKF_GO1_ONLY     diagnostic / A-B variants under another name
 # Product build: kernels.hip is compiled once per kernel set (-DDEKF_KSET=<bit> -DDEKF_KSET_ONLY: the unit carries only its set;
-# bit 1024 = the kernels that are not solves, bit 2048 = the innovation kernels of dekf_set_innovation, bit 4096 = the gate kernels of dekf_set_innovation_gate, bit 8192 = the snapshot kernels of dekf_save_instances) next to dekf_capi.hip, DEKF_JOBS units at a time (default: all of them at once — they
+# bit 1024 = the kernels that are not solves, bit 2048 = the innovation kernels of dekf_set_innovation, bit 4096 = the gate kernels of dekf_set_innovation_gate, bit 8192 = the snapshot kernels of dekf_save_instances, bit 16384 = the gate kernels of dekf_set_gate_smoother) next to dekf_capi.hip, DEKF_JOBS units at a time (default: all of them at once — they
 # are independent, no -fgpu-rdc: a kernel is launched through its host stub, which any unit can reference), then linked.  One
 # translation unit of everything takes 4.6 minutes, the slowest set 70 s.
 # DEKF_UNITY=1 compiles both sources as ONE translation unit (variants that select their kernels with -DDEKF_KSET / -DDEKF_GO1_ONLY,
@@ -91,13 +91,21 @@ else
         fi
     }
     run snapshot_unit
+    # The gate kernels of a smoothing gate handle (dekf_set_gate_smoother): one more, remarks in ${OUT%.so}_gate_smooth_resource_usage.txt
+    gate_smooth_unit() {
+        if ! $HIPCC $FLAGS -Rpass-analysis=kernel-resource-usage -c -DDEKF_KSET=16384 -DDEKF_KSET_ONLY -o "$T/k_16384.o" kernels.hip $EXTRA 2> "$T/gate_smooth_ru.txt"; then
+            grep -v "remark:" "$T/gate_smooth_ru.txt" >&2
+            return 1
+        fi
+    }
+    run gate_smooth_unit
     run $HIPCC $FLAGS -c -o "$T/capi.o" dekf_capi.hip "$@"
     rc=0
     for p in "${pids[@]}"; do wait "$p" || rc=1; done
     [ $rc -eq 0 ] || { echo "build failed"; exit 1; }
     $HIPCC --offload-arch=gfx950 -fPIC -shared -o "$OUT" "$T"/*.o -ldl
     # (warnings of the units, if any, to the terminal, without the include chain in front of the solve kernels' remarks; the remarks to the file)
-    cat "$T"/ru_*.txt "$T"/innov_ru.txt "$T"/gate_ru.txt "$T"/snapshot_ru.txt | grep -v "remark:\|^ *[0-9]* | \|^ *| \|^In file included from " >&2 || true
+    cat "$T"/ru_*.txt "$T"/innov_ru.txt "$T"/gate_ru.txt "$T"/snapshot_ru.txt "$T"/gate_smooth_ru.txt | grep -v "remark:\|^ *[0-9]* | \|^ *| \|^In file included from " >&2 || true
     { echo "# compiler resource remarks of $(basename "$OUT"), $(date -u +%Y-%m-%dT%H:%MZ), flags: $FLAGS $EXTRA; no-machine-LICM sets: $NO_MLICM";
       cat "$T"/ru_notes.txt 2>/dev/null || true; cat "$T"/ru_*.txt | grep "remark:" | sed 's/^.*remark: *//; s/ *\[-Rpass-analysis=kernel-resource-usage\]//'; } > "${OUT%.so}_resource_usage.txt"
     { echo "# compiler resource remarks of the innovation kernels of $(basename "$OUT"), $(date -u +%Y-%m-%dT%H:%MZ), flags: $FLAGS $EXTRA";
@@ -106,5 +114,7 @@ else
       grep "remark:" "$T/gate_ru.txt" | sed 's/^.*remark: *//; s/ *\[-Rpass-analysis=kernel-resource-usage\]//'; } > "${OUT%.so}_gate_resource_usage.txt"
     { echo "# compiler resource remarks of the snapshot kernels of $(basename "$OUT"), $(date -u +%Y-%m-%dT%H:%MZ), flags: $FLAGS $EXTRA";
       grep "remark:" "$T/snapshot_ru.txt" | sed 's/^.*remark: *//; s/ *\[-Rpass-analysis=kernel-resource-usage\]//'; } > "${OUT%.so}_snapshot_resource_usage.txt"
+    { echo "# compiler resource remarks of the gate kernels of a smoothing gate handle of $(basename "$OUT"), $(date -u +%Y-%m-%dT%H:%MZ), flags: $FLAGS $EXTRA";
+      grep "remark:" "$T/gate_smooth_ru.txt" | sed 's/^.*remark: *//; s/ *\[-Rpass-analysis=kernel-resource-usage\]//'; } > "${OUT%.so}_gate_smooth_resource_usage.txt"
 fi
 echo "built $(pwd)/$OUT"

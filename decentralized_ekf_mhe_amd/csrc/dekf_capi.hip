@@ -15,6 +15,7 @@
 #include "mhe_direct_core.h"
 #include "mhe_epoch_core.h"
 #include "mhe_gate_core.h"
+#include "mhe_gate_window_core.h"
 #include "mhe_innov_core.h"
 #include "mhe_params_core.h"
 #include "mhe_pause_core.h"
@@ -59,6 +60,17 @@ DEKF_GATE_KERNEL(2)
 DEKF_GATE_KERNEL(3)
 DEKF_GATE_KERNEL(4)
 #undef DEKF_GATE_KERNEL
+// the gate kernels of a smoothing gate handle (mhe_gate_window_core.h): the gate kernel's body with the window correction behind it
+#define DEKF_GATE_SMOOTH_KERNEL(L)                                                                                                \
+    __global__ void k_mhe_innov_gate_##L##_smooth(DevCfg c, DevState s, int kstart, int K, double* cov, InnovStore out, GateStore gs, \
+                                                  DirectWindow win);                                                             \
+    __global__ void k_mhe_innov_gate_##L##_smooth_ep(DevCfg c, DevState s, int T, double* cov, InnovStore out, GateStore gs,     \
+                                                     const int* t0, const DevCfg* pc, DirectWindow win);
+DEKF_GATE_SMOOTH_KERNEL(1)
+DEKF_GATE_SMOOTH_KERNEL(2)
+DEKF_GATE_SMOOTH_KERNEL(3)
+DEKF_GATE_SMOOTH_KERNEL(4)
+#undef DEKF_GATE_SMOOTH_KERNEL
 __global__ void k_gap();
 __global__ void k_kf_initialize(DevCfg c, DevState s);
 __global__ void k_kf_update(DevCfg c, DevState s, int pushes);
@@ -151,6 +163,10 @@ struct dekf_handle_s {
     // count (mhe_gate_core.h) in place of the innovation kernel.  gate_st.gated: [B][L] ints, allocated by the first call that
     // switches the gate on, zeroed by dekf_reset and, for the restarted instances, by dekf_reset_instances
     GateStore gate_st;
+    // dekf_set_gate_smoother: a gating handle that smooths.  The option switches `smoother` on with it (the handle is a smoothing handle
+    // in every other respect) and makes the handle launch the gate kernel's _smooth twin (mhe_gate_window_core.h), which carries the
+    // gate's correction down win.x / win.cov with the T1_k the smoothing kernel left in win.t1.  True only with smoother and a bound > 0
+    bool gate_smoother = false;
     // dekf_save_instances, dekf_load_instances: the state map (mhe_snapshot_core.h), every persistent per-instance array of `s`
     // (host_common.h: state_map, at dekf_create) and the stores above, each appended where it is allocated
     StateMap snap_map;
@@ -336,6 +352,14 @@ typedef void (*GateEpochFn)(DevCfg, DevState, int, double*, InnovStore, GateStor
 struct GateKernel { GateFn fn; GateEpochFn fn_ep; };
 const GateKernel gate_kernels[DEKF_MAX_LEGS] = {{k_mhe_innov_gate_1, k_mhe_innov_gate_1_ep}, {k_mhe_innov_gate_2, k_mhe_innov_gate_2_ep},
                                                 {k_mhe_innov_gate_3, k_mhe_innov_gate_3_ep}, {k_mhe_innov_gate_4, k_mhe_innov_gate_4_ep}};
+// Their _smooth twins as dekf_set_gate_smoother selects them: the gate kernels' arguments, then the window stores
+typedef void (*GateSmoothFn)(DevCfg, DevState, int, int, double*, InnovStore, GateStore, DirectWindow);
+typedef void (*GateSmoothEpochFn)(DevCfg, DevState, int, double*, InnovStore, GateStore, const int*, const DevCfg*, DirectWindow);
+struct GateSmoothKernel { GateSmoothFn fn; GateSmoothEpochFn fn_ep; };
+const GateSmoothKernel gate_smooth_kernels[DEKF_MAX_LEGS] = {{k_mhe_innov_gate_1_smooth, k_mhe_innov_gate_1_smooth_ep},
+                                                             {k_mhe_innov_gate_2_smooth, k_mhe_innov_gate_2_smooth_ep},
+                                                             {k_mhe_innov_gate_3_smooth, k_mhe_innov_gate_3_smooth_ep},
+                                                             {k_mhe_innov_gate_4_smooth, k_mhe_innov_gate_4_smooth_ep}};
 
 // the kernel of its row that a direct handle launches: the variant of the list with the handle's smoother and cross settings and the
 // clock of its instance mode
@@ -363,19 +387,23 @@ struct SolveLaunch {
     // ... or, on a gating handle (dekf_set_innovation_gate), the gate kernel of its leg count IN PLACE of the innovation kernel (null:
     // none; `innov` is then null): the same grid, lds_innov of LDS.  The epoch twin takes the parameter table, or null
     const GateKernel* gate;
+    // ... or, on a gating handle that smooths (dekf_set_gate_smoother), that kernel's _smooth twin IN PLACE of it (null: none; `gate` is
+    // then null): the same grid, lds_innov of LDS, which is then the larger size of the window correction
+    const GateSmoothKernel* gate_smooth;
 };
 SolveLaunch solve_launch(const dekf_handle_s* h, int K) {
     if (h->solver == DEKF_SOLVER_DIRECT) {
         const DirectVariant v = direct_variant(h);
         const bool gate = h->innov && h->gate_st.nis_leg_max > 0.0;
+        const bool gate_smooth = gate && h->smoother && h->gate_smoother;
         return {h->direct->name[v], h->c.B, 64, h->lds_direct, nullptr, v, h->innov && !gate ? &innov_kernels[h->c.L - 1] : nullptr,
-                (size_t)(gate ? GateScratch::len(h->c.L) : InnovScratch::len(h->c.L)) * sizeof(double),
-                gate ? &gate_kernels[h->c.L - 1] : nullptr};
+                (size_t)(gate_smooth ? GateWindowScratch::len(h->c.L) : (gate ? GateScratch::len(h->c.L) : InnovScratch::len(h->c.L))) * sizeof(double),
+                gate && !gate_smooth ? &gate_kernels[h->c.L - 1] : nullptr, gate_smooth ? &gate_smooth_kernels[h->c.L - 1] : nullptr};
     }
     const bool full = h->solve_entry_full && K == h->c.N;
     const SolveTwin t = solve_twin(full ? h->solve_entry_full : h->solve_entry, h->c.polish != 0, h->c.warm != 0);
-    if (full) return {t.name, h->solve_grid_full, h->solve_threads_full, h->lds_solve_full, t.fn, dv_count, nullptr, 0, nullptr};
-    return {t.name, h->solve_grid, DEKF_SOLVE_THREADS, h->lds_solve, t.fn, dv_count, nullptr, 0, nullptr};
+    if (full) return {t.name, h->solve_grid_full, h->solve_threads_full, h->lds_solve_full, t.fn, dv_count, nullptr, 0, nullptr, nullptr};
+    return {t.name, h->solve_grid, DEKF_SOLVE_THREADS, h->lds_solve, t.fn, dv_count, nullptr, 0, nullptr, nullptr};
 }
 
 // A family of full-window kernels (K == N): the shapes it covers are the rows of its role in solve_kernels.def
@@ -583,6 +611,14 @@ void launch_solve(dekf_handle h, const SolveLaunch& l, const DevState& sp, int T
         else
             l.gate->fn_ep<<<l.grid, 64, l.lds_innov, ss>>>(h->c, sp, T, h->mhe_cov, h->innov_st, h->gate_st, h->inst.t0,
                                                            direct_variants[l.variant].clock == Clock::PARAM ? h->inst.pp_mhe : nullptr);
+        return;
+    }
+    if (l.gate_smooth) {  // (a gating handle that smooths: the same launch, with the correction of the window the solve just left)
+        if (direct_variants[l.variant].clock == Clock::WINDOW)
+            l.gate_smooth->fn<<<l.grid, 64, l.lds_innov, ss>>>(h->c, sp, kstart, K, h->mhe_cov, h->innov_st, h->gate_st, h->win);
+        else
+            l.gate_smooth->fn_ep<<<l.grid, 64, l.lds_innov, ss>>>(h->c, sp, T, h->mhe_cov, h->innov_st, h->gate_st, h->inst.t0,
+                                                                  direct_variants[l.variant].clock == Clock::PARAM ? h->inst.pp_mhe : nullptr, h->win);
         return;
     }
     if (!l.innov) return;
@@ -1558,11 +1594,26 @@ dekf_status dekf_set_solver(dekf_handle h, int solver) {
     h->solver = solver;
     h->mhe_cov_valid = false;
     if (solver == DEKF_SOLVER_ADMM) {  // the smoother, its cross-covariances, the innovation statistics and their gate are the direct solve's
-        h->smoother = h->cross = h->innov = false;
+        h->smoother = h->cross = h->innov = h->gate_smoother = false;
         h->gate_st.nis_leg_max = 0.0;
     }
     h->innov_valid = false;
     h->win_steps = 0;
+    return DEKF_OK;
+}
+
+// the window smoother's stores and their entries of the state map, at the first call that needs them (dekf_set_smoother,
+// dekf_set_gate_smoother)
+static dekf_status smoother_stores(dekf_handle h) {
+    if (h->win.x) return DEKF_OK;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t B = (size_t)h->c.B, N = (size_t)h->c.N, ns = (size_t)h->c.ns;
+    TRY(dev_alloc(h, B * (N * ns + (2 * N - 1) * ns * ns) * sizeof(double), &h->win.x));  // x | cov | t1 in one block
+    h->win.cov = h->win.x + B * N * ns;
+    h->win.t1 = h->win.cov + B * N * ns * ns;
+    h->snap_map.add(h->win.x, h->c.N * h->c.ns, 8, SNAP_INSTANCE_MAJOR, SNAP_TAG_WIN_X);
+    h->snap_map.add(h->win.cov, h->c.N * h->c.ns * h->c.ns, 8, SNAP_INSTANCE_MAJOR, SNAP_TAG_WIN_COV);
+    h->snap_map.add(h->win.t1, (h->c.N - 1) * h->c.ns * h->c.ns, 8, SNAP_INSTANCE_MAJOR, SNAP_TAG_WIN_T1);
     return DEKF_OK;
 }
 
@@ -1573,19 +1624,26 @@ dekf_status dekf_set_smoother(dekf_handle h, int on) {
         return fail(DEKF_ERR_INVALID, "the window smoother cannot be combined with the innovation gate (dekf_set_innovation_gate)");
     if (on && h->solver != DEKF_SOLVER_DIRECT) return fail(DEKF_ERR_INVALID, "the window smoother needs a direct handle (dekf_set_solver(h, DEKF_SOLVER_DIRECT))");
     if (h->initialized) return fail(DEKF_ERR_ORDER, "dekf_set_smoother is allowed before dekf_initialize or right after dekf_reset");
-    if (on && !h->win.x) {
-        HIPCHK(hipSetDevice(h->device));
-        const size_t B = (size_t)h->c.B, N = (size_t)h->c.N, ns = (size_t)h->c.ns;
-        TRY(dev_alloc(h, B * (N * ns + (2 * N - 1) * ns * ns) * sizeof(double), &h->win.x));  // x | cov | t1 in one block
-        h->win.cov = h->win.x + B * N * ns;
-        h->win.t1 = h->win.cov + B * N * ns * ns;
-        h->snap_map.add(h->win.x, h->c.N * h->c.ns, 8, SNAP_INSTANCE_MAJOR, SNAP_TAG_WIN_X);
-        h->snap_map.add(h->win.cov, h->c.N * h->c.ns * h->c.ns, 8, SNAP_INSTANCE_MAJOR, SNAP_TAG_WIN_COV);
-        h->snap_map.add(h->win.t1, (h->c.N - 1) * h->c.ns * h->c.ns, 8, SNAP_INSTANCE_MAJOR, SNAP_TAG_WIN_T1);
-    }
+    if (on) TRY(smoother_stores(h));
     h->smoother = on != 0;
-    if (!on) h->cross = false;  // the cross-covariances are the smoother's: switched off with it
+    if (!on) h->cross = h->gate_smoother = false;  // the cross-covariances and the gate's window are the smoother's: switched off with it
     h->win_steps = 0;
+    return DEKF_OK;
+}
+
+dekf_status dekf_set_gate_smoother(dekf_handle h, int on) {
+    if (!h) return fail(DEKF_ERR_INVALID, "null handle");
+    if (on != 0 && on != 1) return fail(DEKF_ERR_INVALID, "dekf_set_gate_smoother: on must be 0 or 1");
+    if (on && !(h->innov && h->gate_st.nis_leg_max > 0.0))
+        return fail(DEKF_ERR_INVALID, "dekf_set_gate_smoother needs a gating handle (dekf_set_innovation_gate with a bound > 0)");
+    if (on && h->smoother && !h->gate_smoother)
+        return fail(DEKF_ERR_INVALID, "dekf_set_gate_smoother(h, 1) needs the smoother off: it switches it on itself");
+    if (h->initialized) return fail(DEKF_ERR_ORDER, "dekf_set_gate_smoother is allowed before dekf_initialize or right after dekf_reset");
+    if (on) TRY(smoother_stores(h));
+    if (on || h->gate_smoother) {  // (off on a handle without the option leaves a smoothing handle as it is)
+        h->smoother = h->gate_smoother = on != 0;
+        h->win_steps = 0;
+    }
     return DEKF_OK;
 }
 
@@ -1593,6 +1651,8 @@ dekf_status dekf_set_window_cross(dekf_handle h, int on) {
     if (!h) return fail(DEKF_ERR_INVALID, "null handle");
     if (on != 0 && on != 1) return fail(DEKF_ERR_INVALID, "dekf_set_window_cross: on must be 0 or 1");
     if (on && !h->smoother) return fail(DEKF_ERR_INVALID, "the window cross-covariances need a smoothing handle (dekf_set_smoother(h, 1))");
+    if (on && h->gate_smoother)
+        return fail(DEKF_ERR_INVALID, "the window cross-covariances cannot be combined with dekf_set_gate_smoother: their backward pass overwrites T1_k");
     if (h->initialized) return fail(DEKF_ERR_ORDER, "dekf_set_window_cross is allowed before dekf_initialize or right after dekf_reset");
     if (on && !h->cross_st.newest) {
         HIPCHK(hipSetDevice(h->device));
@@ -1655,6 +1715,10 @@ dekf_status dekf_set_innovation(dekf_handle h, int on) {
     h->innov = on != 0;
     h->innov_valid = false;
     if (!on) h->gate_st.nis_leg_max = 0.0;  // the gate is the statistics': switched off with them
+    if (!on && h->gate_smoother) {          // ... and with the gate its window and the smoother that came with it
+        h->smoother = h->gate_smoother = false;
+        h->win_steps = 0;
+    }
     return DEKF_OK;
 }
 
@@ -1663,7 +1727,7 @@ dekf_status dekf_set_innovation_gate(dekf_handle h, double nis_leg_max) {
     if (!(nis_leg_max >= 0.0) || !(nis_leg_max <= 1.7976931348623157e308))
         return fail(DEKF_ERR_INVALID, "dekf_set_innovation_gate: nis_leg_max must be finite and not negative (0 switches the gate off)");
     if (nis_leg_max > 0.0 && !h->innov) return fail(DEKF_ERR_INVALID, "the innovation gate needs an innovation handle (dekf_set_innovation(h, 1))");
-    if (nis_leg_max > 0.0 && h->smoother) return fail(DEKF_ERR_INVALID, "the innovation gate cannot be combined with the window smoother (dekf_set_smoother)");
+    if (nis_leg_max > 0.0 && h->smoother && !h->gate_smoother) return fail(DEKF_ERR_INVALID, "the innovation gate cannot be combined with the window smoother (dekf_set_smoother)");
     if (h->initialized) return fail(DEKF_ERR_ORDER, "dekf_set_innovation_gate is allowed before dekf_initialize or right after dekf_reset");
     if (nis_leg_max > 0.0 && !h->gate_st.gated) {
         HIPCHK(hipSetDevice(h->device));
@@ -1673,6 +1737,10 @@ dekf_status dekf_set_innovation_gate(dekf_handle h, double nis_leg_max) {
         h->snap_map.add(h->gate_st.gated, h->c.L, 4, SNAP_INSTANCE_MAJOR, SNAP_TAG_GATED);
     }
     h->gate_st.nis_leg_max = nis_leg_max;
+    if (!(nis_leg_max > 0.0) && h->gate_smoother) {  // the gate's window goes with the gate, and the smoother that came with it
+        h->smoother = h->gate_smoother = false;
+        h->win_steps = 0;
+    }
     return DEKF_OK;
 }
 

@@ -8,6 +8,8 @@
 //                     (mhe_solve_core.h, mhe_admm_core.h)
 //   k_mhe_solve_direct_*  the direct solve (dekf_set_solver), one wavefront per instance: rows x variants of direct_kernels.def (mhe_direct_core.h)
 //   k_mhe_innov_*     the innovation statistics behind the direct solve (dekf_set_innovation), one wavefront per instance (mhe_innov_core.h)
+//   k_mhe_innov_gate_*  the innovation gate in place of the innovation kernel (dekf_set_innovation_gate, mhe_gate_core.h); _smooth: with
+//                     the gate's correction carried down the smoothed window (dekf_set_gate_smoother, mhe_gate_window_core.h)
 //   k_kf_*            KF alternative                      (kf_core.h)
 //   k_latch_vo        masked VO latch (robotSub::vo_callback for a batch)
 //   k_latch4          device-to-device sensor latch of one push (IMU or leg arrays) in one launch
@@ -26,6 +28,7 @@
 #include "mhe_epoch_core.h"
 #include "mhe_innov_core.h"
 #include "mhe_gate_core.h"
+#include "mhe_gate_window_core.h"
 #include "mhe_params_core.h"
 #include "mhe_pause_core.h"
 #include "mhe_snapshot_core.h"
@@ -144,6 +147,12 @@ extern "C" {
 #define DEKF_SNAPSHOT_KERNELS 1
 #else
 #define DEKF_SNAPSHOT_KERNELS 0
+#endif
+// ... and the gate kernels of a smoothing gate handle (dekf_set_gate_smoother) only with bit 16384: the same again
+#if !defined(DEKF_KSET_ONLY) || (defined(DEKF_KSET) && (DEKF_KSET & 16384))
+#define DEKF_GATE_SMOOTH_KERNELS 1
+#else
+#define DEKF_GATE_SMOOTH_KERNELS 0
 #endif
 #if DEKF_MISC_KERNELS
 __global__ void __launch_bounds__(64) k_ekf_tick(DevCfg c, DevState s, int count) {
@@ -376,6 +385,43 @@ DEKF_GATE_KERNEL(3)
 DEKF_GATE_KERNEL(4)
 #undef DEKF_GATE_KERNEL
 #endif  // DEKF_GATE_KERNELS
+
+#if DEKF_GATE_SMOOTH_KERNELS
+// The gate kernels of a smoothing gate handle (dekf_set_gate_smoother, mhe_gate_window_core.h): what such a handle launches IN PLACE
+// of the gate kernel of its leg count, behind the direct kernel's _smooth twin.  The body of k_mhe_innov_gate_L[_ep] and, for an
+// instance that gated a leg, gate_window_t in the same wavefront: the gate's correction carried down the window the smoothing kernel
+// has just left (win).  An instance that gates nothing runs the gate kernel's instructions and no more.  The epoch twin takes K from
+// direct_window_epoch.  A set of their own (bit 16384), carried by every build without -DDEKF_KSET_ONLY: the eight gate kernels stay
+// the code they were.
+#define DEKF_GATE_SMOOTH_KERNEL(L)                                                                                            \
+    __global__ void __launch_bounds__(64) k_mhe_innov_gate_##L##_smooth(DevCfg c, DevState s, int kstart, int K, double* cov, \
+                                                                        InnovStore out, GateStore gs, DirectWindow win) {    \
+        extern __shared__ double lds[];                                                                                      \
+        const int slot = (kstart + K - 1) % c.wcap;                                                                          \
+        const bool solved = innovation_t<L>(c, s, blockIdx.x, slot, cov, out, lds);                                          \
+        bool corrected = false;                                                                                              \
+        if (gate_t<L>(c, c, s, blockIdx.x, slot, cov, out, gs, solved, lds, &corrected))                                     \
+            gate_window_t<L>(c, blockIdx.x, K, corrected, win, lds);                                                         \
+    }                                                                                                                        \
+    __global__ void __launch_bounds__(64) k_mhe_innov_gate_##L##_smooth_ep(DevCfg c, DevState s, int T, double* cov, InnovStore out, \
+                                                                           GateStore gs, const int* t0,                      \
+                                                                           const DevCfg* __restrict__ pc, DirectWindow win) { \
+        extern __shared__ double lds[];                                                                                      \
+        int kstart, K;                                                                                                       \
+        if (direct_window_epoch(c, T, t0[blockIdx.x], kstart, K)) {                                                          \
+            const int slot = (kstart + K - 1) % c.wcap;                                                                      \
+            const bool solved = innovation_t<L>(c, s, blockIdx.x, slot, cov, out, lds);                                      \
+            bool corrected = false;                                                                                          \
+            if (gate_t<L>(c, pc ? pc[blockIdx.x] : c, s, blockIdx.x, slot, cov, out, gs, solved, lds, &corrected))           \
+                gate_window_t<L>(c, blockIdx.x, K, corrected, win, lds);                                                     \
+        }                                                                                                                    \
+    }
+DEKF_GATE_SMOOTH_KERNEL(1)
+DEKF_GATE_SMOOTH_KERNEL(2)
+DEKF_GATE_SMOOTH_KERNEL(3)
+DEKF_GATE_SMOOTH_KERNEL(4)
+#undef DEKF_GATE_SMOOTH_KERNEL
+#endif  // DEKF_GATE_SMOOTH_KERNELS
 
 #if DEKF_SNAPSHOT_KERNELS
 // The snapshot kernels (dekf_save_instances, dekf_load_instances; mhe_snapshot_core.h).  A grid of (n, chunks) workgroups of 256 lanes:

@@ -31,9 +31,13 @@ struct GateStore {
 };
 
 // LDS of one instance (doubles): the innovation core's, then fl (4) | D (9) | D^-1 (9) | D^-1 - P_vv (9) | its inverse (9) | w (3) |
-// P E K (27) | P (81) | P' (81) | x' (9) | d (3) | scratch of the lane-sequential inverse (6)
+// P E K (27) | P (81) | P' (81) | x' (9) | d (3) | scratch of the lane-sequential inverse (6).  The constants are the fields' offsets
+// behind the innovation core's part: what a gated instance leaves there (Km, w, the ungated P, P' and x' of a correction that
+// succeeded) is what the window correction of a smoothing gate handle reads (mhe_gate_window_core.h).
 struct GateScratch {
-    static constexpr int OWN = 4 + 4 * 9 + 3 + 27 + 2 * 81 + 9 + 3 + 6;
+    static constexpr int FL = 0, D = FL + 4, DI = D + 9, KN = DI + 9, KM = KN + 9, W = KM + 9, PK = W + 3, P = PK + 27, PN = P + 81,
+                         XN = PN + 81, DD = XN + 9, SCR = DD + 3;
+    static constexpr int OWN = SCR + 6;
     DEKF_HD static int len(int L) { return InnovScratch::len(L) + OWN; }
 };
 
@@ -42,23 +46,25 @@ DEKF_FN double gate_sym3(const double* A, int i, int j) { return i <= j ? A[3 * 
 
 // The gate of instance b behind its innovation statistics (`solved`: what innovation_t returned).  cq: the configuration that holds
 // the instance's Q_swing (the handle's, or the instance's row of the parameter table).  sm: GateScratch::len(L) doubles of LDS, of
-// which the innovation core has used the first InnovScratch::len(L).  Returns the number of gated legs.
+// which the innovation core has used the first InnovScratch::len(L).  Returns the number of gated legs.  corrected (may be null):
+// where legs were gated, whether the correction succeeded (group-uniform); untouched where none was.
 template <int L>
 DEKF_FN int gate_t(const DevCfg& c, const DevCfg& cq, const DevState& s, int b, int slot, double* cov, const InnovStore& out,
-                   const GateStore& gs, bool solved, double* sm) {
+                   const GateStore& gs, bool solved, double* sm, bool* corrected = nullptr) {
     constexpr int NM = 3 * L;
-    double* fl = sm + InnovScratch::len(L);  // 1.0 for a gated leg
-    double* D = fl + 4;
-    double* Di = D + 9;
-    double* Kn = Di + 9;   // D^-1 - P_vv
-    double* Km = Kn + 9;   // its inverse
-    double* w = Km + 9;
-    double* PK = w + 3;    // P E K, 9 x 3
-    double* P = PK + 27;
-    double* Pn = P + 81;
-    double* xn = Pn + 81;
-    double* d = xn + 9;
-    double* scr = d + 3;
+    double* const gm = sm + InnovScratch::len(L);
+    double* fl = gm + GateScratch::FL;  // 1.0 for a gated leg
+    double* D = gm + GateScratch::D;
+    double* Di = gm + GateScratch::DI;
+    double* Kn = gm + GateScratch::KN;   // D^-1 - P_vv
+    double* Km = gm + GateScratch::KM;   // its inverse
+    double* w = gm + GateScratch::W;
+    double* PK = gm + GateScratch::PK;   // P E K, 9 x 3
+    double* P = gm + GateScratch::P;
+    double* Pn = gm + GateScratch::PN;
+    double* xn = gm + GateScratch::XN;
+    double* d = gm + GateScratch::DD;
+    double* scr = gm + GateScratch::SCR;
     int* const gated = gs.gated + (size_t)L * b;
     // the decision, by the lane that wrote the leg's NIS (NaN compares false: a failed solve or innovation gates nothing)
     wfor(L, [&](int leg) {
@@ -145,6 +151,7 @@ DEKF_FN int gate_t(const DevCfg& c, const DevCfg& cq, const DevState& s, int b, 
         if (!ok) s.status[b] = DEKF_SOLVE_NUMERIC;
     }
     DEKF_SYNC();
+    if (corrected) *corrected = ok;
     return ng;
 }
 

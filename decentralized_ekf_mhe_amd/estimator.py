@@ -57,7 +57,8 @@ def relative_cov(cov_win, cov_newest, k):
 
 class BatchedEstimator:
     def __init__(self, params: DekfParams, batch: int, device: int = 0, stream=None, warm_start: bool = False, solver: str = "admm",
-                 smoother: bool = False, cross: bool = False, innovation: bool = False, innovation_gate: float = 0.0):
+                 smoother: bool = False, cross: bool = False, innovation: bool = False, innovation_gate: float = 0.0,
+                 gate_smoother: bool = False):
         """warm_start: full-window solves start from the previous tick's shifted solution (dekf_set_warm_start; off by default).
         solver: "admm" (default, the reference's OSQP-style ADMM) or "direct" (the exact optimum of the window QP and its covariance,
         dekf_set_solver; see mhe_cov)
@@ -67,7 +68,9 @@ class BatchedEstimator:
         innovation: a direct handle also leaves the innovation of the newest leg measurement, its covariance, the NIS (whole and per
         leg) and the predictive log-likelihood of every tick (dekf_set_innovation; see innovation)
         innovation_gate: an innovation handle takes a stance leg whose per-leg NIS exceeds this bound out of the solve, as if it had been
-        in swing at that tick (dekf_set_innovation_gate; see innovation_gate).  0.0: off.  Without innovation=True the library refuses it"""
+        in swing at that tick (dekf_set_innovation_gate; see innovation_gate).  0.0: off.  Without innovation=True the library refuses it
+        gate_smoother: a gating handle also smooths; the gate's correction is carried down the window (dekf_set_gate_smoother; see
+        window).  Without innovation_gate > 0, or with smoother=True, the library refuses it"""
         if solver not in ("admm", "direct"):
             raise ValueError(f"solver must be 'admm' or 'direct', not {solver!r}")
         _torch_runtime_first()
@@ -90,6 +93,8 @@ class BatchedEstimator:
                 capi.check(self.lib.dekf_set_innovation(self.h, 1))
             if innovation_gate != 0.0:
                 capi.check(self.lib.dekf_set_innovation_gate(self.h, float(innovation_gate)))
+            if gate_smoother:
+                capi.check(self.lib.dekf_set_gate_smoother(self.h, 1))
             if warm_start:
                 capi.check(self.lib.dekf_set_warm_start(self.h, 1))
         except capi.DekfError:
@@ -333,6 +338,10 @@ class BatchedEstimator:
         bound = C.c_double(0.0)
         capi.check(self.lib.dekf_get_innovation_gate(self.h, C.byref(bound), C.c_void_p(gated.ctypes.data), capi.DEKF_HOST))
         return bound.value, gated
+
+    def set_gate_smoother(self, on):
+        """switch the window of a gating handle on or off (dekf_set_gate_smoother; before initialize() or right after reset())"""
+        capi.check(self.lib.dekf_set_gate_smoother(self.h, int(on)))
 
     def kf_cov(self):
         ns = self.params.dim_state

@@ -549,6 +549,40 @@ dekf_status dekf_get_innovation(dekf_handle h, double* innov, double* innov_cov,
 dekf_status dekf_set_innovation_gate(dekf_handle h, double nis_leg_max);
 dekf_status dekf_get_innovation_gate(dekf_handle h, double* nis_leg_max, int* gated, dekf_mem where);
 
+/* ---- the window of a gating handle (opt-in, gating handles): carry the gate's correction down the smoothed window ------------
+ * One more additive symbol: DEKF_ABI_VERSION and dekf_params are unchanged, and a caller that never calls it launches exactly the
+ * kernels of before and gets the same bits.  dekf_set_smoother and dekf_set_innovation_gate refuse each other as the section above
+ * says; this call is the exception to it.  Gating a leg at step T changes the newest block's information alone, the smoother's gains
+ * of the older steps do not read step T's measurement, and its backward recursion is affine in the newest state and covariance: the
+ * gate's rank-3 correction of the posterior runs down the window as a rank-3 correction of every block.
+ * dekf_set_gate_smoother(h, 1) needs a gating handle (dekf_set_innovation_gate with a bound > 0, hence a direct innovation handle with
+ * leg_odom_type 0) whose smoother is off, else DEKF_ERR_INVALID; after dekf_initialize DEKF_ERR_ORDER (call order as for
+ * dekf_set_smoother); DEKF_ERR_INVALID for a null handle and a value other than 0 or 1.  Calling it again is allowed.  The handle
+ * becomes a smoothing handle: the first enable allocates the smoother's stores, dekf_solve_kernel_name names the _smooth twin,
+ * dekf_get_window works as on any smoothing handle, and the setting survives dekf_reset.  dekf_set_gate_smoother(h, 0) switches the
+ * option and the smoother off; the gate stays on.  While the option is on:
+ *  - dekf_set_smoother(h, 0) switches both off; dekf_set_smoother(h, 1) stays DEKF_ERR_INVALID;
+ *  - dekf_set_innovation_gate(h, 0) switches the gate, the option and the smoother off; a positive value changes the bound (this is
+ *    the only smoothing handle on which that call is allowed);
+ *  - dekf_set_window_cross(h, 1) is DEKF_ERR_INVALID: its backward pass overwrites the gains this correction reads;
+ *  - dekf_set_innovation(h, 0) and dekf_set_solver(h, DEKF_SOLVER_ADMM) switch everything off, as they do without the option.
+ * Such a handle's update launches the direct kernel's _smooth twin and, IN PLACE of k_mhe_innov_gate_<L>[_ep], its twin
+ * k_mhe_innov_gate_<L>_smooth[_ep]; timing class 2 brackets both as before.
+ * The contract, per instance and update.  An instance that gates nothing: the kernel touches nothing but gated, and the window is the
+ * smoothing kernel's.  An instance that gates: x_win[b][k] and cov_win[b][k], k = 0 .. K-1, become the state blocks of the optimum of
+ * the window QP with the gated legs' swing blocks (the QP whose newest block the gate returns) and their covariances; x_win[b][K-1] is
+ * bit-identical to x_mhe[b], cov_win[b][K-1] to the instance's block of dekf_get_mhe_cov, and every cov_win[b][k] is symmetric to the
+ * bit.  A failed correction (the gate's DEKF_SOLVE_NUMERIC) gives NaN in all K entries of both arrays, as a failed smoother does.
+ * Everything else (x_mhe, v_b, status, solver info, dekf_get_mhe_cov, the five arrays of dekf_get_innovation, gated and the record
+ * edit) is bit-identical to the same gating handle without the option.  At every update at which an instance gates nothing, its
+ * window too is bit-identical to that of a smoothing innovation handle without the gate fed the log with contact = 0 at every
+ * (tick, leg) this instance gated before.  A paused instance keeps every bit; a restarted one behaves as on a smoothing handle and
+ * on a gating handle; a parameter table is honoured as the gate honours it.
+ * Snapshots: the blob format is unchanged (its header already carries the smoother setting and the bound); a blob of such a handle
+ * loads into a handle with the same settings and is refused by any other, as today.
+ * Not part of this interface: cross-covariances of a gating handle; ADMM and KF handles; leg_odom_type 1. */
+dekf_status dekf_set_gate_smoother(dekf_handle h, int on);
+
 /* ---- snapshots of single instances (direct handles): one robot leaves its slot, its handle, its process -----------------------
  * Three more additive symbols: DEKF_ABI_VERSION and dekf_params are unchanged, and a caller that never calls them launches exactly the
  * kernels of before and gets the same bits.  An instance can be restarted, paused and given its own noise; with these it can also be

@@ -4,7 +4,7 @@
     python tools/device_code_digest.py [--src TREE] [--jobs N] [--out FILE]
 
 Host-only (no GPU).  Compiles TREE's kernels.hip once per unit of the product build (build.sh: -DDEKF_KSET=<mask> -DDEKF_KSET_ONLY,
-masks 1 ... 512, 1024, 2048, with -mllvm -disable-machine-licm for the sets build.sh compiles without that pass) as device code
+masks 1 ... 512, 1024 ... 16384, with -mllvm -disable-machine-licm for the sets build.sh compiles without that pass) as device code
 alone, disassembles every unit and prints, sorted by name,
 
     <symbol> <sha256 of the instruction encodings, addresses left out> <metadata fields>
@@ -21,7 +21,7 @@ import subprocess
 import sys
 import tempfile
 
-MASKS = [512, 256, 128, 64, 32, 16, 8, 4, 1, 2, 1024, 2048]  # heaviest first, as build.sh
+MASKS = [512, 256, 128, 64, 32, 16, 8, 4, 1, 2, 1024, 2048, 4096, 8192, 16384]  # heaviest first, as build.sh
 NO_MLICM = {1, 2, 4, 64, 128, 256, 512}  # build.sh: DEKF_NO_MLICM's default
 META = ["kernarg_segment_size", "vgpr_count", "sgpr_count", "agpr_count", "vgpr_spill_count", "sgpr_spill_count",
         "private_segment_fixed_size", "group_segment_fixed_size", "max_flat_workgroup_size", "uses_dynamic_stack"]

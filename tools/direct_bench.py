@@ -21,6 +21,12 @@ alternate inside one process, so that a drift of the machine does not land on on
                                                      # (dekf_set_innovation_gate; profiles/r11_gate_bench.jsonl).  The log then carries a
                                                      # few foot slips (every 512th robot, three ticks) and the bound is high, so the
                                                      # common path is "decide, gate nothing"; gated_last: legs gated at the last step
+    python tools/direct_bench.py go1 cassie pogox --modes direct_smooth_innov,direct_smooth_innov_gate_window --repeat 3
+                                                     # the window of a gating handle (dekf_set_gate_smoother;
+                                                     # profiles/r15_gate_smoother_bench.jsonl): the smoother with the innovation kernel
+                                                     # against the same with the gate kernel's _smooth twin, on the slip-carrying log.
+                                                     # --gate-bound 150 prices the gated path itself; gated_total: legs gated over the
+                                                     # timed steps
 --epoch measures what dekf_reset_instances costs the instances it does not restart: per mode ONE handle runs the unchanged direct
 kernel (`before`), then restarts instance 0, lets its window refill and runs the epoch twins (`after`); dekf_reset brings the handle
 back, and the two alternate --repeat times in one process.  One JSON line per shape (--out: profiles/r11_epoch_bench.jsonl).
@@ -64,7 +70,10 @@ SHAPES = {
 MODES = {"cold": dict(), "warm": dict(warm_start=True), "direct": dict(solver="direct"),
          "direct_smooth": dict(solver="direct", smoother=True), "direct_cross": dict(solver="direct", smoother=True, cross=True),
          "direct_innov": dict(solver="direct", innovation=True),
-         "direct_innov_gate": dict(solver="direct", innovation=True, innovation_gate=1e4)}
+         "direct_innov_gate": dict(solver="direct", innovation=True, innovation_gate=1e4),
+         "direct_smooth_innov": dict(solver="direct", smoother=True, innovation=True),
+         "direct_smooth_innov_gate_window": dict(solver="direct", innovation=True, innovation_gate=1e4, gate_smoother=True)}
+GATE_MODES = ("direct_innov_gate", "direct_smooth_innov_gate_window")
 GATE_SLIP = (-12.8, 8.0, -5.4)   # m/s, IMU frame: far above the bound on every shape (nis_leg of 4e4 and more)
 
 
@@ -101,13 +110,17 @@ def one(p, B, sd, W, steps, mode):
         est2.step(k)
     est2.sync()
     est2.timing_enable(1)
+    gated_total = 0
     for k in range(W, W + steps):
         est2.push_stream_step(sd, k)
         est2.step(k)
+        if mode in GATE_MODES:  # (a read between the steps of the pass that is timed by events around the launches alone)
+            gated_total += int(est2.innovation_gate()[1].sum())
     tim = est2.timing_read()
     solved = float((est2.get()["status"] == 1).mean())
     kernel = est.solve_kernel_name(True)
-    gated = {"gated_last": int(est2.innovation_gate()[1].sum())} if mode == "direct_innov_gate" else {}
+    gated = {"gated_last": int(est2.innovation_gate()[1].sum()), "gated_total": gated_total,
+             "gate_bound": MODES[mode]["innovation_gate"]} if mode in GATE_MODES else {}
     est.close()
     est2.close()
     return {"steps_per_s": B * steps / dt, "solve_ms": tim["solve"][0] / max(tim["solve"][1], 1),
@@ -340,9 +353,13 @@ def main():
     ap.add_argument("--epoch", action="store_true", help="the same handle before and after a first dekf_reset_instances")
     ap.add_argument("--instance-params", action="store_true", help="the same handle without and with a table of B distinct parameter sets")
     ap.add_argument("--snapshot", action="store_true", help="dekf_save_instances / dekf_load_instances of the whole batch against a device-to-device copy")
+    ap.add_argument("--gate-bound", type=float, default=None, help="the bound of the gating modes (default 1e4: almost nothing gates)")
     ap.add_argument("--paused", default=None, help="with --epoch: fractions of the batch to pause (dekf_set_active), e.g. 0,0.5,0.9")
     a = ap.parse_args()
     modes = a.modes.split(",")
+    if a.gate_bound is not None:
+        for m in GATE_MODES:
+            MODES[m]["innovation_gate"] = a.gate_bound
     fractions = [float(f) for f in a.paused.split(",")] if a.paused else []
     if fractions and not a.epoch:
         ap.error("--paused goes with --epoch")
@@ -355,7 +372,8 @@ def main():
     if a.out is None and a.epoch:
         a.out = os.path.join(ROOT, "profiles", "r11_epoch_bench.jsonl")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "r11_gate_bench.jsonl" if "direct_innov_gate" in modes else
+        a.out = os.path.join(ROOT, "profiles", "r15_gate_smoother_bench.jsonl" if "direct_smooth_innov_gate_window" in modes else
+                             "r11_gate_bench.jsonl" if "direct_innov_gate" in modes else
                              "r10_innovation_bench.jsonl" if "direct_innov" in modes else
                              "r10_cross_bench.jsonl" if "direct_cross" in modes else
                              "r09_smoother_bench.jsonl" if "direct_smooth" in modes else "r08_direct_bench.jsonl")
@@ -407,7 +425,7 @@ def main():
             continue
         W = max(p.N + 10, 64)  # (as tools/bench_shapes.py: past the window fill and the first vision intervals)
         s = make_streams(p, B, W + a.steps)
-        if "direct_innov_gate" in modes:  # (every mode of the line runs the same log)
+        if any(m in modes for m in GATE_MODES + ("direct_smooth_innov",)):  # (every mode of the line runs the same log)
             s = add_slips(s, W, a.steps)
         sd = streams_to_device(s)
         line = {"shape": name, "batch": B, "N": int(p.N), "steps": a.steps}
@@ -435,6 +453,9 @@ def main():
                 if m in line:
                     line[f"gate_solve_ms_over_{tag}"] = line["direct_innov_gate"]["solve_ms"] / line[m]["solve_ms"]
                     line[f"gate_steps_per_s_over_{tag}"] = line["direct_innov_gate"]["steps_per_s"] / line[m]["steps_per_s"]
+        if "direct_smooth_innov_gate_window" in line and "direct_smooth_innov" in line:  # (class 2: the solve and the kernel behind it)
+            line["gate_window_solve_ms_over_smooth_innov"] = line["direct_smooth_innov_gate_window"]["solve_ms"] / line["direct_smooth_innov"]["solve_ms"]
+            line["gate_window_steps_per_s_over_smooth_innov"] = line["direct_smooth_innov_gate_window"]["steps_per_s"] / line["direct_smooth_innov"]["steps_per_s"]
         if "direct_cross" in line:
             for m, tag in (("direct", "direct"), ("direct_smooth", "smooth")):
                 if m in line:
